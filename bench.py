@@ -6,12 +6,24 @@ each, australia8_mf hyperparameters). One step = one GP posterior update of
 every seed (simulator.py:888-892): append the k = 8 agents' new hifi samples to
 N_L = 1024 lofi + 1016 hifi points (N = 2048), update the factor, and compute
 the posterior mean and variance at all M = 16384 grid cells. Inputs are
-resident in HBM before the timed region. After the timed steps each rank's
+resident in HBM before the timed region. With --full, after the timed steps each rank's
 per-seed max-variance trajectory (the VarMax log, simulator.py:925) is
 all-gathered over RCCL for the loss/variance aggregation of runner.py:144-147.
 
-Two update paths are timed back to back on the same workload, with identical
-results (tests/test_gpu_incremental.py, tests/test_gpu_lattice*.py):
+A plain run does what the headline figure needs and no more: set-up, the warm-up
+steps, the --steps timed steps of the `value` path below, and one JSON line with
+metric, value, unit, higher_is_better, dtype and ms_per_step (one timed step's
+wall time). A run longer than the grid has distinct sample cells for takes its
+steps' inputs round robin.
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/mu.npy, DIR/var.npy ([seeds, M], float64) and DIR/var_max.npy ([seeds]); the
+inputs depend on the arguments alone, so two builds can be compared array for array.
+--full adds the rest of the report, each part a run of its own after the timed
+region: the full_recompute comparison, the roofline and per-stage passes, the
+trajectory gather, the simulation leg and the CPU baselines.
+
+With --full two update paths are timed back to back on the same workload, with
+identical results (tests/test_gpu_incremental.py, tests/test_gpu_lattice*.py):
   value          -- the library's default path. On the headline's lattice grid
                     that is the lattice-separable step,
                     two launches per step at B = 8 (k_inc_lat_arg: bordered-
@@ -35,8 +47,9 @@ headline (configs[3] sizes, fp64).
 (python -m torch.distributed.run as a child; this process never touches the GPU)
 and exits with their status. Under a launcher WORLD_SIZE must equal N.
 The timed region holds exactly the K steps (a barrier + device synchronisation
-on both sides, no HIP events inside); the trajectory gather runs after it and is
-reported on its own (gather_ms).
+on both sides, no HIP events inside); with --full the trajectory gather runs
+after it and is reported on its own (gather_ms).
+The figures below are part of the --full report.
 roofline (value): the step's kernel, HBM-bound (k_inc_lat: F's lower triangle
   streamed once, the posterior in / out, the new V rows, the Z rows; k_inc_stream:
   the resident V read once) over its average launch time from HIP events on the
@@ -122,7 +135,13 @@ def parse():
     p.add_argument("--dtype", choices=["f64", "f32"], default=None)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-faithful", type=int, default=1, help="also time the reference-faithful op sequence")
-    p.add_argument("--no-full", action="store_true", help="skip the full-recompute comparison run")
+    p.add_argument("--no-full", action="store_true", help="with --full: skip the full-recompute comparison run")
+    p.add_argument("--full", action="store_true",
+                   help="the whole report: besides the headline run, the full-recompute comparison, the roofline "
+                        "and per-stage passes, the trajectory gather, the simulation leg and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (mu, var, var_max) "
+                        "as DIR/<name>.npy")
     p.add_argument("--diagnostic", action="store_true",
                    help="allow a diagnostic library (MFGP_LIB); its line is marked and is not a headline number")
     a = p.parse_args()
@@ -134,7 +153,11 @@ def parse():
         if getattr(a, key) is None:
             setattr(a, key, v)
     if a.full_steps is None:
-        a.full_steps = a.steps
+        # the reference's per-update work is ~200x the incremental step's: its comparison
+        # run follows --steps up to the headline's default and stays there for longer runs
+        a.full_steps = min(a.steps, 200)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -394,6 +417,107 @@ def simulation_leg(a, world, rank, my_seeds, wls, hyp, dev, backend):
     }
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: the most one run writes, over all ranks and arrays
+
+
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs: this rank's arrays as DIR/<name>.npy (DIR/<name>_rank<r>.npy
+    with more than one rank), float64. Arrays that would take the run past
+    DUMP_BYTES are written as a fixed sample: the elements at sorted indices drawn
+    without replacement by default_rng(0), the same for every run of one shape."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // world
+    size = 8 * sum(v.size for v in arrays.values())
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if size > budget:
+            keep = max(1, int(v.size * budget / size))
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), v)
+
+
+def step_roofline(a, inc, lattice, g2, default_cfg, c4_cfg, B, M, N, NL, G, k, K):
+    """The roofline block of the incremental step (--full): its algorithmic bytes and
+    flops over the launch time of the event-timed pass, with the committed counter
+    summary of this build where there is one."""
+    elapsed, tm = inc["elapsed"], inc["tm"]
+    f32 = a.dtype == "f32"
+    n0 = N - k
+    es = 4 if f32 else 8
+    # algorithmic bytes of one k_inc_stream launch: V_old read once, V_new written,
+    # grid read and mu / var written, and per training row the L21 gather, its
+    # store into A and read back, the compact rows and z
+    if f32:
+        vbytes = B * (4 * M * (n0 + k) + 32 * M + n0 * (16 * k + 4 * 16 + 8))
+    else:
+        vbytes = B * 8 * (M * (n0 + k + 4) + n0 * (3 * k + 1))
+    # (sub-batches on concurrent streams: a launch covers B / streams GPs)
+    shr = inc["gps_per_launch"] / B
+    vbytes = vbytes * shr
+    v_ms = tm["predict_ms"] / max(1, tm["predict_launches"])
+    v_gbs = vbytes / (v_ms * 1e-3) / 1e9 if v_ms > 0 else float("nan")
+    # the lattice step in axis form (k_inc_lat, DESIGN.md section 2.4). Bytes: F's
+    # lower triangle read once by the w pass (the dominant stream; es bytes per element), the resident
+    # posterior in and out plus the caller's mu / var, the new V rows, the Z rows
+    # written once and read by every 64-column tile row; flops: the w pass (16 n0^2),
+    # the Z sums (2 KA nx n_t) and the K = parts x ny GEMM (2 KA M parts ny8)
+    ka = 8 if k <= 8 else 16
+    parts = 2
+    n_t = n0 + (n0 - NL)
+    ny8 = -(-G // 8) * 8
+    # (F's elements: fp32 for MFGP_F32 models, whose w units stream the rounded copy)
+    fbytes = es * sum((n0 - 64 * jb) * 64 for jb in range(-(-n0 // 64)))
+    zbytes = 8 * parts * ny8 * G * ka * (1 + -(-G // 64))
+    lat_bytes = B * (fbytes + 8 * 6 * M + es * M * k + zbytes) * shr
+    lat_flops = B * (16 * n0 * n0 + 2 * ka * G * n_t + 2 * ka * M * parts * ny8) * shr
+    lat_gbs = lat_bytes / (v_ms * 1e-3) / 1e9 if v_ms > 0 else float("nan")
+    lat_tf = lat_flops / (v_ms * 1e-3) / 1e12 if v_ms > 0 else float("nan")
+    kern = "k_inc_lat" if lattice else ("k_inc_stream" if FUSED else "k_vstream")
+    if lattice and g2:
+        kern = ("k_inc_lat", "k_lat_gemm2")
+    # PMC bytes come from the committed profile of the default configuration
+    traffic, traffic_src = None, None
+    if default_cfg or c4_cfg:
+        # batches of <= 8 GPs run the step with its descriptors as the kernel argument
+        # (k_inc_lat_arg, k_lat_gemm2_arg); larger ones upload them (k_inc_lat, k_lat_gemm2)
+        if lattice and B <= 8:
+            ka_ = ("k_inc_lat_arg", "k_lat_gemm2_arg") if g2 else "k_inc_lat_arg"
+            traffic, traffic_src = pmc_traffic(ka_, "configs4" if c4_cfg else None)
+            if traffic is not None:
+                kern = ka_
+        if traffic is None:
+            traffic, traffic_src = pmc_traffic(kern, "configs4" if c4_cfg else None)
+    kern = kern if isinstance(kern, str) else " + ".join(kern)
+    if lattice:
+        roof = {"bound": "hbm", "achieved": lat_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": lat_gbs / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "kernel": kern, "bytes_per_launch": lat_bytes, "flops_per_launch": lat_flops,
+                "mfma_tflops": lat_tf, "avg_launch_ms": v_ms, "launches_timed": tm["predict_launches"],
+                "timing": f"HIP events around each of {inc['R']} launches of an untimed pass after the timed "
+                          "region (no events inside the timed region)",
+                "design_note": "bytes = F's lower triangle (the w pass), the posterior in / out, the new V rows "
+                               "and the Z rows; avg_launch_ms spans the step's launches (HIP events before the "
+                               "first, after the last); the step is a chain of dependent phases (producers -> "
+                               "w -> Z | GEMM -> cells), latency- not bandwidth-bound (DESIGN.md section 2.4)"}
+    else:
+        roof = {"bound": "hbm", "achieved": v_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": v_gbs / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "kernel": kern, "bytes_per_launch": vbytes, "avg_launch_ms": v_ms,
+                "launches_timed": tm["predict_launches"],
+                "timing": f"HIP events around each of {inc['R']} launches of an untimed pass after the timed "
+                          "region (no events inside the timed region)",
+                "design_bytes_note": f"{es}-byte V: bytes_per_launch = the resident V read once plus the new "
+                                     "rows, grid, outputs and per-row L21 / z terms (DESIGN.md section 4)"}
+    # the step's algorithmic bytes over the whole step's wall time (all sub-batches)
+    step_bytes = roof["bytes_per_launch"] / shr
+    roof["streams"] = inc["streams"]
+    if roof.get("traffic"):
+        roof["traffic_over_algorithmic"] = roof["traffic"] / roof["bytes_per_launch"]
+    roof["step_aggregate_gbs"] = step_bytes / (elapsed / K) / 1e9
+    roof["step_aggregate_frac"] = roof["step_aggregate_gbs"] / PEAK_HBM_GBS
+    return roof
+
+
 def main():
     a = parse()
     plan, arg = launch_plan(a.gpus, os.environ)
@@ -447,14 +571,18 @@ def main():
     hyp = synthetic.HYP[a.hyp]
     M = G * G
     N = NL + NH
-    wls = [synthetic.Workload(G, NL, NH0, k, total, seed=seed) for seed in my_seeds]
-    Xnew = torch.from_numpy(np.ascontiguousarray(np.stack([w.Xnew for w in wls], 1).reshape(total, B * k, 2))).to(dev)
-    ynew = torch.from_numpy(np.ascontiguousarray(np.stack([w.ynew for w in wls], 1).reshape(total, B * k))).to(dev)
+    # a seed's samples are distinct grid cells, so the grid holds (M - NH0) / k steps of
+    # them: a longer run takes its inputs round robin (every step truncates back to the
+    # base rows first, so any step's samples are a valid update)
+    n_in = max(1, min(total, (M - NH0) // k))
+    wls = [synthetic.Workload(G, NL, NH0, k, n_in, seed=seed) for seed in my_seeds]
+    Xnew = torch.from_numpy(np.ascontiguousarray(np.stack([w.Xnew for w in wls], 1).reshape(n_in, B * k, 2))).to(dev)
+    ynew = torch.from_numpy(np.ascontiguousarray(np.stack([w.ynew for w in wls], 1).reshape(n_in, B * k))).to(dev)
     mu = torch.empty(B * M, dtype=torch.float64, device=dev)
     var = torch.empty(B * M, dtype=torch.float64, device=dev)
     ks = [k] * B
 
-    def run(incremental, W, K, nstreams=1):
+    def run(incremental, W, K, nstreams=1, dump=False):
         total = W + K
         # the rank's seeds as `nstreams` contiguous sub-batches, each stepped by its
         # own context on its own stream (concurrent launches: mfgp_ctx_set_concurrent);
@@ -496,11 +624,12 @@ def main():
                 c.synchronize()
 
         def step(s):
+            si = s % n_in
             for g in range(NS):
                 lo = glo[g]
                 batches[g].truncate(NH0)
                 # VarMax of every seed (np.amax(cov), simulator.py:1014) fused into the predict epilogue
-                batches[g].append_predict(xp0 + 8 * (s * B * k * 2 + lo * k * 2), yp0 + 8 * (s * B * k + lo * k),
+                batches[g].append_predict(xp0 + 8 * (si * B * k * 2 + lo * k * 2), yp0 + 8 * (si * B * k + lo * k),
                                           mup + 8 * lo * M, varp + 8 * lo * M, asynchronous=True,
                                           vmax_ptr=vp0 + 8 * (s * B + lo))
 
@@ -528,10 +657,10 @@ def main():
         lat_build_ms = None
         tw0 = time.perf_counter()
         for s in range(W):
-            if s == 0 and incremental:
+            if s == 0 and incremental and a.full:
                 set_timing(True)
             step(s)
-            if s == 0 and incremental:
+            if s == 0 and incremental and a.full:
                 sync_all()
                 lat_build_ms = timing_all()["factor_ms"]
                 set_timing(False)
@@ -541,9 +670,10 @@ def main():
         # warm_ms of wall time has passed
         extra = 0
         sync_all()
-        aggregate(varmax[:W].transpose(0, 1).contiguous())   # first-use kernel loads / communicator setup
-        sync_all()
-        set_timing(False)
+        if a.full:
+            aggregate(varmax[:W].transpose(0, 1).contiguous())   # first-use kernel loads / communicator setup
+            sync_all()
+            set_timing(False)
         if world > 1:
             dist.barrier()
         # (the warm-up steps end right before the timed region: no idle gap in which
@@ -570,43 +700,57 @@ def main():
         # the job's one exchange (the per-seed VarMax trajectories, runner.py:144-147),
         # once per job: timed on its own, not part of the per-step rate
         traj = varmax[W:].transpose(0, 1).contiguous()           # [B, K] per-seed VarMax trajectory
-        tg0 = time.perf_counter()
-        agg = aggregate(traj)
-        torch.cuda.synchronize(dev)
-        tg1 = time.perf_counter()
+        res = {}
+        tg0 = tg1 = 0.0
+        if a.full:
+            tg0 = time.perf_counter()
+            agg = aggregate(traj)
+            torch.cuda.synchronize(dev)
+            tg1 = time.perf_counter()
+            if not diag_lib:   # diagnostic library builds compute garbage on purpose
+                assert torch.isfinite(agg).all()
         sync_all()   # raises LinAlgError if any factor was not positive definite
-        # the kernel's launch time (roofline): R more untimed steps on the same
-        # inputs, HIP events around every launch on each launch stream
-        R = min(K, 50) if incremental else min(K, 3)
-        set_timing(True, predict_only=True)
-        for s in range(W, W + R):
-            step(s)
-        sync_all()
-        tm = timing_all()
-        # per-stage breakdown: a few more (untimed) steps with every stage bracketed by events
-        set_timing(True)
-        nb_steps = min(5 if incremental else 1, K)
-        for s in range(W, W + nb_steps):
-            step(s)
-        sync_all()
-        tb = timing_all()
-        set_timing(False)
+        if dump:
+            # what the last timed step handed its caller, before any later pass reuses the buffers
+            torch.cuda.synchronize(dev)
+            res["outputs"] = {"mu": mu.view(B, M).cpu().numpy(), "var": var.view(B, M).cpu().numpy(),
+                              "var_max": varmax[total - 1].cpu().numpy()}
+        if a.full:
+            # the kernel's launch time (roofline): R more untimed steps on the same
+            # inputs, HIP events around every launch on each launch stream
+            R = min(K, 50) if incremental else min(K, 3)
+            set_timing(True, predict_only=True)
+            for s in range(W, W + R):
+                step(s)
+            sync_all()
+            tm = timing_all()
+            # per-stage breakdown: a few more (untimed) steps with every stage bracketed by events
+            set_timing(True)
+            nb_steps = min(5 if incremental else 1, K)
+            for s in range(W, W + nb_steps):
+                step(s)
+            sync_all()
+            tb = timing_all()
+            set_timing(False)
+            res.update({"tm": tm, "R": R, "lat_build_ms": lat_build_ms,
+                        "breakdown": {"predict": tb["predict_ms"] / nb_steps / NS,
+                                      "factor": tb["factor_ms"] / nb_steps / NS}})
         el = torch.tensor([t1 - t0, tg1 - tg0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        if not diag_lib:   # diagnostic library builds compute garbage on purpose
-            assert torch.isfinite(agg).all()
         st = models[0].stats()
         del models, batches
-        return {"elapsed": float(el[0].item()), "gather_ms": 1e3 * float(el[1].item()), "tm": tm,
-                "lat_build_ms": lat_build_ms, "extra_warmup_steps": extra, "streams": NS,
-                "gps_per_launch": B / NS,
-                "host_ms": 1e3 * float(np.mean(host_t)), "stats": st, "traj": traj.cpu().numpy(), "R": R,
-                "breakdown": {"predict": tb["predict_ms"] / nb_steps / NS, "factor": tb["factor_ms"] / nb_steps / NS}}
+        res.update({"elapsed": float(el[0].item()), "gather_ms": 1e3 * float(el[1].item()),
+                    "extra_warmup_steps": extra, "streams": NS, "gps_per_launch": B / NS,
+                    "host_ms": 1e3 * float(np.mean(host_t)), "stats": st, "traj": traj.cpu().numpy()})
+        return res
 
-    inc = run(True, W, K, a.streams)
-    full = None if a.no_full else run(False, W, KF)
-    sim = simulation_leg(a, world, rank, my_seeds, wls, hyp, dev, backend) if a.sim_iterations else None
+    inc = run(True, W, K, a.streams, dump=bool(a.dump_outputs))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, inc.pop("outputs"), rank, world)
+    # everything below the headline run belongs to the whole report (--full)
+    full = run(False, W, KF) if a.full and not a.no_full else None
+    sim = simulation_leg(a, world, rank, my_seeds, wls, hyp, dev, backend) if a.full and a.sim_iterations else None
     if os.environ.get("MFGP_BENCH_DUMP") and rank == 0:
         np.savez(os.environ["MFGP_BENCH_DUMP"], inc=inc["traj"], full=full["traj"] if full else inc["traj"])
     if full is not None and rank == 0 and not diag_lib:
@@ -615,72 +759,19 @@ def main():
         np.testing.assert_allclose(inc["traj"][:, :KF], full["traj"], rtol=F32_RTOL if f32 else 1e-9)
 
     if rank == 0:
-        elapsed, tm = inc["elapsed"], inc["tm"]
+        elapsed = inc["elapsed"]
         assert inc["stats"]["inc_factor"] >= K and inc["stats"]["vstream"] >= K, inc["stats"]
-        n0 = N - k
-        es = 4 if f32 else 8
         lattice = inc["stats"].get("lattice", 0) >= K
-        # algorithmic bytes of one k_inc_stream launch: V_old read once, V_new written,
-        # grid read and mu / var written, and per training row the L21 gather, its
-        # store into A and read back, the compact rows and z
-        if f32:
-            vbytes = B * (4 * M * (n0 + k) + 32 * M + n0 * (16 * k + 4 * 16 + 8))
-        else:
-            vbytes = B * 8 * (M * (n0 + k + 4) + n0 * (3 * k + 1))
-        # (sub-batches on concurrent streams: a launch covers B / streams GPs)
-        shr = inc["gps_per_launch"] / B
-        vbytes = vbytes * shr
-        v_ms = tm["predict_ms"] / max(1, tm["predict_launches"])
-        v_gbs = vbytes / (v_ms * 1e-3) / 1e9 if v_ms > 0 else float("nan")
-        # the lattice step in axis form (k_inc_lat). Bytes: F's
-        # lower triangle read once by the w pass (the dominant stream; es bytes per element), the resident
-        # posterior in and out plus the caller's mu / var, the new V rows, the Z rows
-        # written once and read by every 64-column tile row; flops: the w pass (16 n0^2),
-        # the Z sums (2 KA nx n_t) and the K = parts x ny GEMM (2 KA M parts ny8)
-        ka = 8 if k <= 8 else 16
-        parts = 2
-        n_t = n0 + (n0 - NL)
-        ny8 = -(-G // 8) * 8
-        # (F's elements: fp32 for MFGP_F32 models, whose w units stream the rounded copy)
-        fbytes = es * sum((n0 - 64 * jb) * 64 for jb in range(-(-n0 // 64)))
-        zbytes = 8 * parts * ny8 * G * ka * (1 + -(-G // 64))
-        lat_bytes = B * (fbytes + 8 * 6 * M + es * M * k + zbytes) * shr
-        lat_flops = B * (16 * n0 * n0 + 2 * ka * G * n_t + 2 * ka * M * parts * ny8) * shr
-        lat_gbs = lat_bytes / (v_ms * 1e-3) / 1e9 if v_ms > 0 else float("nan")
-        lat_tf = lat_flops / (v_ms * 1e-3) / 1e12 if v_ms > 0 else float("nan")
-        value = total_seeds * K / elapsed
-        # SURVEY.md section 8d's algorithmic cost of one update as the reference
-        # computes it (refactor + V from scratch): F = N^3/3 + M N^2 + 2 N^2 + 4 M N flop,
-        # B_8d = 8 (4M + 3N + 2 N^2) bytes. The incremental path does not do that work
-        # (it reuses the resident V): expressed in F per second it exceeds the f64
-        # MFMA peak, which is the point of the algorithm, not a measurement error.
-        F8d = N ** 3 / 3 + M * N * N + 2 * N * N + 4 * M * N
-        B8d = 8 * (4 * M + 3 * N + 2 * N * N)
-        # PMC bytes come from the committed profile of the default configuration
-        default_cfg = (a.workload, G, NL, NH, B, k, a.hyp, a.dtype) == ("headline", 128, 1024, 1024, 8, 8,
-                                                                         "australia8_mf", "f64")
-        c4_cfg = (G, NL, NH, B, a.hyp, a.dtype) == (256, 4096, 4096, 32, "australia9_mf", "f32")
         # the lattice step is two launches (k_inc_lat: producers, w, Z; k_lat_gemm2: the
         # GEMM and cells) where k_lat_gemm2's tiles fill the chip once or twice (the
         # library's rule, mfgp_capi.hip), else one (the GEMM inside k_inc_lat);
         # MFGP_LAT_GEMM2=1 / 0 forces either
         # (the model's lattice_g2 counter says which ran)
         g2 = inc["stats"].get("lattice_g2", 0) >= K
-        kern = "k_inc_lat" if lattice else ("k_inc_stream" if FUSED else "k_vstream")
-        if lattice and g2:
-            kern = ("k_inc_lat", "k_lat_gemm2")
-        traffic, traffic_src = None, None
-        if default_cfg or c4_cfg:
-            # batches of <= 8 GPs run the step with its descriptors as the kernel argument
-            # (k_inc_lat_arg, k_lat_gemm2_arg); larger ones upload them (k_inc_lat, k_lat_gemm2)
-            if lattice and B <= 8:
-                ka_ = ("k_inc_lat_arg", "k_lat_gemm2_arg") if g2 else "k_inc_lat_arg"
-                traffic, traffic_src = pmc_traffic(ka_, "configs4" if c4_cfg else None)
-                if traffic is not None:
-                    kern = ka_
-            if traffic is None:
-                traffic, traffic_src = pmc_traffic(kern, "configs4" if c4_cfg else None)
-        kern = kern if isinstance(kern, str) else " + ".join(kern)
+        value = total_seeds * K / elapsed
+        default_cfg = (a.workload, G, NL, NH, B, k, a.hyp, a.dtype) == ("headline", 128, 1024, 1024, 8, 8,
+                                                                         "australia8_mf", "f64")
+        c4_cfg = (G, NL, NH, B, a.hyp, a.dtype) == (256, 4096, 4096, 32, "australia9_mf", "f32")
         if lattice:
             update = ("incremental, lattice-separable, " + ("two launches per step (k_inc_lat: append, w, Z; "
                       "k_lat_gemm2: GEMM + cells)" if g2 else "one launch per step (k_inc_lat)") +
@@ -688,36 +779,11 @@ def main():
                       "w = K11^-1 K12 from the resident L^-1; every training term lies on the grid's lattice, so "
                       "L21 V_old = sum over lattice rows of Z (w c ex summed per row) times axis-table rows: a "
                       "K = 2 ny f64 MFMA GEMM, no pass over V; mean / variance updated from the previous posterior")
-            roof = {"bound": "hbm", "achieved": lat_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": lat_gbs / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                    "kernel": kern, "bytes_per_launch": lat_bytes, "flops_per_launch": lat_flops,
-                    "mfma_tflops": lat_tf, "avg_launch_ms": v_ms, "launches_timed": tm["predict_launches"],
-                    "timing": f"HIP events around each of {inc['R']} launches of an untimed pass after the timed "
-                              "region (no events inside the timed region)",
-                    "design_note": "bytes = F's lower triangle (the w pass), the posterior in / out, the new V rows "
-                                   "and the Z rows; avg_launch_ms spans the step's launches (HIP events before the "
-                                   "first, after the last); the step is a chain of dependent phases (producers -> "
-                                   "w -> Z | GEMM -> cells), latency- not bandwidth-bound (DESIGN.md section 2.4)"}
         else:
             update = ("incremental, one launch per step (k_inc_stream): bordered-Cholesky append + one pass over "
                       "the resident V = L^-1 psi^T" if FUSED else
                       "incremental: bordered-Cholesky append (k_inc_stream) + one pass over the resident "
                       "V = L^-1 psi^T (k_vstream)")
-            roof = {"bound": "hbm", "achieved": v_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": v_gbs / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                    "kernel": kern, "bytes_per_launch": vbytes, "avg_launch_ms": v_ms,
-                    "launches_timed": tm["predict_launches"],
-                    "timing": f"HIP events around each of {inc['R']} launches of an untimed pass after the timed "
-                              "region (no events inside the timed region)",
-                    "design_bytes_note": f"{es}-byte V: bytes_per_launch = the resident V read once plus the new "
-                                         "rows, grid, outputs and per-row L21 / z terms (DESIGN.md section 4)"}
-        # the step's algorithmic bytes over the whole step's wall time (all sub-batches)
-        step_bytes = roof["bytes_per_launch"] / shr
-        roof["streams"] = inc["streams"]
-        if roof.get("traffic"):
-            roof["traffic_over_algorithmic"] = roof["traffic"] / roof["bytes_per_launch"]
-        roof["step_aggregate_gbs"] = step_bytes / (elapsed / K) / 1e9
-        roof["step_aggregate_frac"] = roof["step_aggregate_gbs"] / PEAK_HBM_GBS
         if default_cfg:
             wl_name = "australia8_mf MFGP seed ensemble (BASELINE configs[3])"
         elif c4_cfg:
@@ -743,12 +809,23 @@ def main():
                             f"samples appended per update), factor update + mean/var at every cell, "
                             + ("MFGP_F32: V = L^-1 psi^T stored and streamed in fp32, factor / solves / "
                                "reductions in fp64" if f32 else "fp64"),
-                "update": update + "; full_recompute below is the reference's per-update work",
+                "update": update + ("; full_recompute below is the reference's per-update work" if a.full else ""),
                 "seeds_per_gpu": B, "grid": G, "N_train": N, "N_lofi": NL, "N_hifi": NH, "agents": k,
                 "global_seeds": total_seeds, "parallelism": f"seed-sharded x{world}, 1 RCCL all_gather",
             },
-            "roofline": roof,
-            "algorithmic_8d": {
+            "host_enqueue_ms_per_step": inc["host_ms"],
+            "extra_warmup_steps": inc["extra_warmup_steps"],
+        }
+        if a.full:
+            out["roofline"] = step_roofline(a, inc, lattice, g2, default_cfg, c4_cfg, B, M, N, NL, G, k, K)
+            # SURVEY.md section 8d's algorithmic cost of one update as the reference
+            # computes it (refactor + V from scratch): F = N^3/3 + M N^2 + 2 N^2 + 4 M N flop,
+            # B_8d = 8 (4M + 3N + 2 N^2) bytes. The incremental path does not do that work
+            # (it reuses the resident V): expressed in F per second it exceeds the f64
+            # MFMA peak, which is the point of the algorithm, not a measurement error.
+            F8d = N ** 3 / 3 + M * N * N + 2 * N * N + 4 * M * N
+            B8d = 8 * (4 * M + 3 * N + 2 * N * N)
+            out["algorithmic_8d"] = {
                 "flops_per_update": F8d, "bytes_per_update": B8d,
                 "flop_equivalent_tflops": F8d * value / 1e12,
                 "frac_of_f64_mfma_peak": F8d * value / 1e12 / PEAK_F64_TFLOPS,
@@ -756,12 +833,9 @@ def main():
                 "note": "SURVEY.md 8d's per-update work is the reference's (refactor + V from scratch); the "
                         "incremental path does not recompute V, so this flop-equivalent rate is above the MFMA "
                         "peak by construction; the roofline above is the kernel's own work",
-            },
-            "host_enqueue_ms_per_step": inc["host_ms"],
-            "extra_warmup_steps": inc["extra_warmup_steps"],
-            "gather_ms": inc["gather_ms"],
-            "breakdown_ms_per_step": inc["breakdown"],
-        }
+            }
+            out["gather_ms"] = inc["gather_ms"]
+            out["breakdown_ms_per_step"] = inc["breakdown"]
         if full is not None:
             ft = full["tm"]
             flops = B * (M * N * N + 4 * M * N)
@@ -785,7 +859,7 @@ def main():
             }
         if sim is not None:
             out["simulation"] = sim
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if M * N > 16384 * 2048:
                 out["cpu_baseline"] = cpu_baseline_sampled(wls[0], hyp, W, NL, NH0, k)
             else:

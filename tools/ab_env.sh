@@ -10,7 +10,7 @@ mkdir -p gpurun_out/ab
 VAR=$1; VALS=$2; ROUNDS=${3:-2}; shift 3 || shift $#
 for r in $(seq 1 $ROUNDS); do
   for v in $VALS; do
-    env $VAR=$v timeout -k 10 300 python -u bench.py --steps 300 --warmup 30 --no-full --no-cpu-baseline "$@" \
+    env $VAR=$v timeout -k 10 300 python -u bench.py --full --steps 300 --warmup 30 --no-full --no-cpu-baseline "$@" \
       > gpurun_out/ab/${VAR}_${v}_$r.json 2> gpurun_out/ab/${VAR}_${v}_$r.err || { echo "run $VAR=$v failed"; tail -20 gpurun_out/ab/${VAR}_${v}_$r.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], round(d['value']), round(d['ms_per_step']*1e3,1), round(d['roofline']['avg_launch_ms']*1e3,1))" \
       gpurun_out/ab/${VAR}_${v}_$r.json "$VAR=$v"

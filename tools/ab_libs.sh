@@ -3,13 +3,14 @@
 # usage (GPU box): bash tools/ab_libs.sh name1 name2 ...   (each run bounded)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
-mkdir -p gpurun_out
+O=${OUT:-$R/ab_out}
+mkdir -p $O
 for rep in 1 2; do
 for v in "$@"; do
   L=$R/tools/stamps_lib/libmfgp_$v.so; [ -f "$L" ] || L=$R/build/libmfgp_$v.so
   [ "$v" = "default" ] && L=$R/mfgp_coverage_amd/libmfgp_hip.so
-  MFGP_LIB=$L timeout -k 10 120 python -u bench.py --diagnostic --no-full --no-cpu-baseline --steps 300 --warmup 30 > gpurun_out/ab_$v.json 2> gpurun_out/ab_$v.err || { echo "$v failed rc=$?"; tail -5 gpurun_out/ab_$v.err; exit 1; }
-  python - "$v" gpurun_out/ab_$v.json <<'PY'
+  MFGP_LIB=$L timeout -k 10 120 python -u bench.py --full --diagnostic --no-full --no-cpu-baseline --steps 300 --warmup 30 > $O/ab_$v.json 2> $O/ab_$v.err || { echo "$v failed rc=$?"; tail -5 $O/ab_$v.err; exit 1; }
+  python - "$v" $O/ab_$v.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 r = d["roofline"]

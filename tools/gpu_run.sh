@@ -40,13 +40,13 @@ for step in "$@"; do
            run 1200 ${O}_tests.log python -u -m pytest -v --timeout 600 --timeout-method thread -m gpu tests/ -k "$K"
            tail -3 ${O}_tests.log ;;
     smoke) run 300 ${O}_smoke.log python -c "import __graft_entry__ as g; g.smoke()"; tail -1 ${O}_smoke.log ;;
-    bench) run 400 ${O}_bench.log python -u bench.py
+    bench) run 400 ${O}_bench.log python -u bench.py --full
            grep '^{' ${O}_bench.log > ${O}_bench.json ;;
-    bench20) run 300 ${O}_bench20.log python -u bench.py --steps 20 --warmup 5
+    bench20) run 300 ${O}_bench20.log python -u bench.py --full --steps 20 --warmup 5
            grep '^{' ${O}_bench20.log > ${O}_bench20.json ;;
-    quick) run 300 ${O}_quick.log python -u bench.py --steps 200 --warmup 20 --no-full --no-cpu-baseline --sim-iterations 0
+    quick) run 300 ${O}_quick.log python -u bench.py --full --steps 200 --warmup 20 --no-full --no-cpu-baseline --sim-iterations 0
            grep '^{' ${O}_quick.log > ${O}_quick.json ;;
-    configs4) run 600 ${O}_configs4.log python -u bench.py --workload configs4
+    configs4) run 600 ${O}_configs4.log python -u bench.py --full --workload configs4
            grep '^{' ${O}_configs4.log > ${O}_configs4.json ;;
     dropin) : > ${O}_dropin.jsonl   # default, then without the early return, then the V stream
            for v in "MFGP_EARLY_PD=1" "MFGP_EARLY_PD=0" "MFGP_LATTICE=0" "MFGP_EARLY_PD=1"; do
