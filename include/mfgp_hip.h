@@ -229,22 +229,27 @@ int mfgp_batch_append_factor(mfgp_model** models, int count, const double* X, co
                              const int64_t* k, int flags);
 int mfgp_batch_predict(mfgp_model** models, int count, double* mu, double* var, int flags);
 /* compute_sample_points (simulator.py:326-374), the Choi planner's sample-set
- * selection, on the device: on a copy of `model` (the model is unchanged),
+ * selection, on the device: past the model's own rows (dropped at the end, with
+ * what else the loop overwrote restored: the model is unchanged, no copy is made),
  * repeatedly append the grid cell of maximal posterior variance (first argmax)
  * with its posterior mean as the observation, until the maximal variance is
  * <= threshold or max_points points were chosen. points: [max_points, 2], host
  * or device; *count = points chosen. Each iteration is a 1-row bordered append
  * and a one-pass predict; the loop runs in chunks on the device (one host
  * synchronisation per 32 iterations). Needs the grid set and incremental
- * updates enabled. */
+ * updates enabled. On any error (MFGP_ERR_NOT_PD from a step of the loop included)
+ * the model is as before the call, and points / count are unspecified. */
 int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, double* points, int64_t* count);
 /* mfgp_sample_points for `count` models stepped together (the Choi planner of many
  * Monte-Carlo seeds, sim:326-374 once per seed): per iteration one decision launch
  * for all models and one batched 1-row append + predict (the lattice step where
  * the batch takes it); each model stops at its own thresholds[b] (host or device)
- * or after max_points points, and is unchanged (each works on a copy). points:
+ * or after max_points points, and is unchanged (each appends past its own rows,
+ * which are dropped and its state restored at the end). points:
  * [count][max_points][2], host or device; counts[b] = points chosen for model b.
- * The models share one context and dtype and need their grids set. */
+ * The models share one context and dtype and need their grids set. On any error
+ * (one model's step not positive definite included) every model is as before the
+ * call, and points / counts are unspecified. */
 int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thresholds, int64_t max_points,
                              double* points, int64_t* counts);
 /* Keep only the first n_keep_hifi hifi rows (no refactor; benchmark reset). */

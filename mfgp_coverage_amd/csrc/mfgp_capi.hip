@@ -2518,7 +2518,9 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
 // model's rows restores it. What the loop overwrites that a truncate does not bring
 // back is saved and restored: the resident posterior (both ping-pong buffers and
 // their tags: the lattice steps write them), the kept result's validity, the path
-// counters (the loop's steps go to the context's planner counters instead). A copy
+// counters (the loop's steps go to the context's planner counters instead), the
+// factor's and V's extent (a failed loop returns through the same restore: on any
+// error the model is as before the call). A copy
 // of A, V and F (~320 MB per model at 128 x 128, N = 2048) and the allocations it
 // took cost more than the whole loop (profiles/r06a_choi: ~36 of 44 ms for 8 seeds).
 struct PlanSave {
@@ -2528,6 +2530,8 @@ struct PlanSave {
   uint64_t res_gen[2], res_tick[2], tick;
   int res_depth[2];
   bool spec_valid, spec_max, pred_since_append;
+  bool factored;
+  int64_t factor_N, v_n;
   int64_t cnt[9];
 };
 static void plan_counters(const mfgp_model* m, int64_t (&v)[9]) {
@@ -2552,13 +2556,25 @@ static int plan_enter(mfgp_model* m, PlanSave& s, double* room) {
   s.spec_valid = m->spec_valid;
   s.spec_max = m->spec_max;
   s.pred_since_append = m->pred_since_append;
+  s.factored = m->factored;
+  s.factor_N = m->factor_N;
+  s.v_n = m->v_n;
   plan_counters(m, s.cnt);
   return MFGP_OK;
 }
+// The loop's deferred status entries of m (the ASYNC batch steps register them): the
+// loop read the words itself at every chunk's end, and what it found is its caller's
+// to return -- a later mfgp_ctx_synchronize must neither raise it again nor drop the
+// factor of the restored model.
+static void plan_drop_async(mfgp_model* m) {
+  auto& as = m->ctx->async_status;
+  as.erase(std::remove_if(as.begin(), as.end(), [m](const mfgp_ctx::AsyncStatus& e) { return e.m == m; }), as.end());
+}
 // back to the model's own rows and state (also after a failed loop: the error is
-// the caller's to return); the loop's path counters go to the context's
-static int plan_leave(mfgp_model* m, const PlanSave& s) {
+// the caller's to return: `failed`); the loop's path counters go to the context's
+static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   m->gate_dev = nullptr;
+  plan_drop_async(m);
   int64_t now[9];
   plan_counters(m, now);
   int64_t* p = m->ctx->plan_stats;
@@ -2581,11 +2597,27 @@ static int plan_leave(mfgp_model* m, const PlanSave& s) {
   m->n_early_pd = s.cnt[8];
   m->NH = s.NH0;
   const int64_t N = m->NL + m->NH;
-  if (m->factored && m->factor_N > N) m->factor_N = N;
-  m->v_n = std::min(m->v_n, N);
+  // the factor of the model's own rows is the one it entered with (the loop wrote
+  // rows past them only, also in a step that failed); V likewise, and what the loop's
+  // first predict built of it stays. INVARIANT this relies on: between plan_enter and
+  // here nothing drops the factor or V's leading rows for real -- ensure_cap keeps a
+  // factored model's factor (its !keep branch needs !factored, and plan_enter runs
+  // after update_factor), ensure_v copies the valid rows when only the capacity grew
+  // (its drop branch needs another grid or no V, and then s.v_n is 0 already), and the
+  // loops fail on "factor lost on growth". A path that could drop either inside the
+  // loop must clear s.factored / s.v_n too, or this restore would resurrect them.
+  m->factored = s.factored;
+  m->factor_N = std::min(s.factor_N, N);
+  m->v_n = std::max(std::min(m->v_n, N), std::min(s.v_n, N));
   m->F_n = std::min(m->F_n, N);
   m->tab_n = std::min(m->tab_n, N);
   m->l21c_N = -1;   // (the compact rows in iscr are the loop's now)
+  if (failed) {
+    // a failed step left its verdict in the status word: the kept factor is a valid
+    // one, and the next loop's first decision reads the word before any append resets it
+    static const int ok = INT_MAX;
+    HIP_TRY(hipMemcpyAsync(m->status, &ok, sizeof(int), hipMemcpyHostToDevice, m->ctx->stream));
+  }
   if (s.res && m->res) {
     HIP_TRY(hipMemcpyAsync(m->res, s.res, sizeof(double) * 4 * m->res_M, hipMemcpyDeviceToDevice, m->ctx->stream));
     for (int b = 0; b < 2; ++b) {
@@ -2623,6 +2655,8 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
   *count = 0;
   mfgp_ctx* c = model->ctx;
   if (!c->incremental) return set_err(MFGP_ERR_ARG, "mfgp_sample_points needs incremental updates enabled");
+  // earlier ASYNC steps' verdicts first: the loop's decisions read the status word
+  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
   if ((rc = update_factor(model))) return rc;
   // the reference works on a deep copy (sim:339); here on the model itself, brought
   // back to its own rows and state at the end (plan_enter / plan_leave)
@@ -2643,7 +2677,8 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
   PlanSave sv;
   if ((rc = plan_enter(t, sv, pts + npt))) return rc;
   auto fail = [&](int code) {
-    (void)plan_leave(t, sv);
+    (void)plan_leave(t, sv, true);
+    (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
     return code;
   };
   // initial posterior (sim:340-342)
@@ -2752,12 +2787,14 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
       if (models[b2] == models[b]) return set_err(MFGP_ERR_ARG, "model %d appears twice in the batch", b);
     counts[b] = 0;
   }
+  // earlier ASYNC steps' verdicts first: the loop's decisions read the status words
+  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
   for (int b = 0; b < count; ++b)
     if ((rc = update_factor(models[b]))) return rc;
   mfgp_model* const* t = models;
   // device state: mu, var [sum M] | vmax [B] | vargmax [B] | state [B][2] | thr [B] | moff [B] |
-  // Ms [B] | grids [B] | xn [B][2] | yn [B] | pos [B] | points [B][max_points][2] | the models'
-  // saved resident posteriors
+  // Ms [B] | grids [B] | status words [B] | xn [B][2] | yn [B] | pos [B] | points [B][max_points][2] |
+  // the models' saved resident posteriors
   std::vector<int64_t> moff(count), Ms(count);
   int64_t Mtot = 0;
   size_t nres = 0;
@@ -2773,7 +2810,7 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   const size_t B_ = (size_t)count;
   const size_t o_mu = 0, o_var = o_mu + (size_t)Mtot, o_vmax = o_var + (size_t)Mtot, o_varg = o_vmax + B_;
   const size_t o_state = o_varg + B_, o_thr = o_state + 2 * B_, o_moff = o_thr + B_, o_Ms = o_moff + B_;
-  const size_t o_grids = o_Ms + B_, o_xn = o_grids + B_, o_yn = o_xn + 2 * B_, o_pos = o_yn + B_;
+  const size_t o_grids = o_Ms + B_, o_stat = o_grids + B_, o_xn = o_stat + B_, o_yn = o_xn + 2 * B_, o_pos = o_yn + B_;
   const size_t o_pts = o_pos + B_, o_res = o_pts + 2 * B_ * (size_t)P, nd = o_res + nres;
   double* ws = nullptr;
   if (hipMalloc(&ws, sizeof(double) * nd) != hipSuccess)
@@ -2781,7 +2818,7 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   std::vector<PlanSave> sv(count);
   int entered = 0;
   auto fail = [&](int code) {
-    for (int b = 0; b < entered; ++b) (void)plan_leave(t[b], sv[b]);
+    for (int b = 0; b < entered; ++b) (void)plan_leave(t[b], sv[b], true);
     (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
     (void)hipFree(ws);
     return code;
@@ -2799,23 +2836,27 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   int64_t* moff_d = reinterpret_cast<int64_t*>(ws + o_moff);
   int64_t* Ms_d = reinterpret_cast<int64_t*>(ws + o_Ms);
   const double** grids_d = reinterpret_cast<const double**>(ws + o_grids);
+  const int** stat_d = reinterpret_cast<const int**>(ws + o_stat);
   double* xn = ws + o_xn;
   double* yn = ws + o_yn;
   int* pos_d = reinterpret_cast<int*>(ws + o_pos);
   double* pts = ws + o_pts;
   std::vector<int64_t> st(2 * count);
   std::vector<const double*> grids(count);
+  std::vector<const int*> stat(count);
   for (int b = 0; b < count; ++b) {
     st[2 * b] = 1;
     st[2 * b + 1] = 0;
     grids[b] = t[b]->grid;
+    stat[b] = t[b]->status;
   }
   hipStream_t s = c->stream;
   if (hipMemcpyAsync(state, st.data(), sizeof(int64_t) * 2 * count, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(thr, thresholds, sizeof(double) * count, hipMemcpyDefault, s) != hipSuccess ||
       hipMemcpyAsync(moff_d, moff.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(Ms_d, Ms.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(grids_d, grids.data(), sizeof(double*) * count, hipMemcpyHostToDevice, s) != hipSuccess)
+      hipMemcpyAsync(grids_d, grids.data(), sizeof(double*) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(stat_d, stat.data(), sizeof(int*) * count, hipMemcpyHostToDevice, s) != hipSuccess)
     return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: state upload failed"));
   // the initial posteriors and their max / argmax (sim:340-342)
   if ((rc = batch_run(const_cast<mfgp_model**>(t), count, nullptr, nullptr, nullptr, mu, var, vmax, vargmax, 0,
@@ -2846,8 +2887,8 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
     if (hipMemcpyAsync(pos_d, pos.data(), sizeof(int) * count, hipMemcpyHostToDevice, s) != hipSuccess)
       return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: upload failed"));
     for (int64_t it = 0; it < C; ++it) {
-      if (launch_choi_select_batch(count, pos_d, state, thr, vmax, vargmax, mu, moff_d, grids_d, Ms_d, xn, yn, pts,
-                                   max_points, s) != hipSuccess)
+      if (launch_choi_select_batch(count, pos_d, state, stat_d, thr, vmax, vargmax, mu, moff_d, grids_d, Ms_d, xn, yn,
+                                   pts, max_points, s) != hipSuccess)
         return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: launch failed"));
       if ((int)lm.size() == count)
         rc = batch_run(lm.data(), count, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true);

@@ -2509,6 +2509,10 @@ __global__ __launch_bounds__(NT) void k_vnarrow(const GPDesc* __restrict__ descs
 // (sim:352-366), unless the maximal variance is at or below the threshold or
 // max_points rows were chosen -- then the loop is over: *gate = 0 and every
 // gated kernel after it is a no-op. state[1] counts the chosen points.
+// The model's status word still holds the previous iteration's verdict here: a
+// failed append (not positive definite, or a hand-off that never arrived) closes
+// the gate too, so no later launch of the chunk resets the word and the host's
+// one read at the chunk's end sees the failure.
 __global__ void k_choi_select(const GPDesc* __restrict__ descs, double threshold, double* __restrict__ points,
                               int64_t max_points) {
   const GPDesc& d = descs[0];
@@ -2516,7 +2520,7 @@ __global__ void k_choi_select(const GPDesc* __restrict__ descs, double threshold
   int64_t* cnt = reinterpret_cast<int64_t*>(d.gate) + 1;
   const double vmax = *d.vmax;
   const int64_t j = *d.vargmax;
-  if (!(vmax > threshold) || *cnt >= max_points || j < 0 || j >= d.M) {
+  if (*d.status != INT_MAX || !(vmax > threshold) || *cnt >= max_points || j < 0 || j >= d.M) {
     *d.gate = 0;
     return;
   }
@@ -2534,9 +2538,10 @@ __global__ void k_choi_select(const GPDesc* __restrict__ descs, double threshold
 // batch from its fused (max, argmax) -- stop at its threshold or its point budget
 // (state[b] = {gate, count}), else take the argmax cell and its posterior mean as the
 // next hifi row, staged in xn / yn at the model's place pos[b] among the batch
-// step's members (its device-source rows), and record it in pts[b][count].
+// step's members (its device-source rows), and record it in pts[b][count]. A model
+// whose previous append failed (status[b], as in k_choi_select) stops as well.
 __global__ void k_choi_select_batch(int count, const int* __restrict__ pos, int64_t* __restrict__ state,
-                                    const double* __restrict__ thr,
+                                    const int* const* __restrict__ status, const double* __restrict__ thr,
                                     const double* __restrict__ vmax, const int64_t* __restrict__ vargmax,
                                     const double* __restrict__ mu, const int64_t* __restrict__ moff,
                                     const double* const* __restrict__ grids, const int64_t* __restrict__ Ms,
@@ -2548,7 +2553,7 @@ __global__ void k_choi_select_batch(int count, const int* __restrict__ pos, int6
   if (st[0] == 0) return;
   const double v = vmax[b];
   const int64_t j = vargmax[b], cnt = st[1];
-  if (!(v > thr[b]) || cnt >= max_points || j < 0 || j >= Ms[b]) {
+  if (*status[b] != INT_MAX || !(v > thr[b]) || cnt >= max_points || j < 0 || j >= Ms[b]) {
     st[0] = 0;
     return;
   }
@@ -2622,12 +2627,13 @@ hipError_t launch_inc_factor(const GPDesc* d, int count, int64_t max_nprod, int 
   else hipLaunchKernelGGL(k_inc_stream<double>, dim3(count, (unsigned)max_nprod), dim3(NT), 0, s, d);
   return hipGetLastError();
 }
-hipError_t launch_choi_select_batch(int count, const int* pos, int64_t* state, const double* thr, const double* vmax,
+hipError_t launch_choi_select_batch(int count, const int* pos, int64_t* state, const int* const* status,
+                                    const double* thr, const double* vmax,
                                     const int64_t* vargmax, const double* mu, const int64_t* moff,
                                     const double* const* grids, const int64_t* Ms, double* xn, double* yn,
                                     double* pts, int64_t max_points, hipStream_t s) {
-  hipLaunchKernelGGL(k_choi_select_batch, dim3((count + 63) / 64), dim3(64), 0, s, count, pos, state, thr, vmax, vargmax,
-                     mu, moff, grids, Ms, xn, yn, pts, max_points);
+  hipLaunchKernelGGL(k_choi_select_batch, dim3((count + 63) / 64), dim3(64), 0, s, count, pos, state, status, thr, vmax,
+                     vargmax, mu, moff, grids, Ms, xn, yn, pts, max_points);
   return hipGetLastError();
 }
 hipError_t launch_choi_select(const GPDesc* d, double threshold, double* points, int64_t max_points,

@@ -19,6 +19,10 @@ Choi planner of a rank's Monte-Carlo seeds: one seed's sample set each): every
 iteration is one decision launch for all of them and one batched 1-row append +
 predict (libmfgp_hip's mfgp_batch_sample_points, the lattice step where the batch
 takes it); each model stops at its own threshold.
+
+On any error (a step that is not positive definite raises LinAlgError, as updt /
+updt_hifi does inside the reference's loop) the models are as before the call, and
+the points are unspecified.
 """
 from __future__ import annotations
 
