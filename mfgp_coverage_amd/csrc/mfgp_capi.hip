@@ -683,6 +683,9 @@ bool lat_cond_ok(const mfgp_model* m) {
   const double noise = (m->kind == MFGP_SF ? h.noiseL : std::min(h.noiseL, h.noiseH)) + h.jitter;
   return noise > 0.0 && h.kss / noise <= LAT_RMAX;
 }
+// table width: 64, 128, 192 or 256 where the step applies (lat_eligible: <= NT). At 192
+// zq rounds down to 2 and a Z unit's second thread group is a partial one (lat_zunit);
+// every width, rectangles and a degenerate axis: tests/test_gpu_lattice_grids.py
 int64_t lat_tabw(const mfgp_model* m) { return round_up(std::max<int64_t>(m->lat.nx, m->lat.ny), 64); }
 int64_t lat_tiles(const mfgp_model* m, int ka) {
   return ((m->lat.nx + 128 / ka - 1) / (128 / ka)) * ((m->lat.ny + 63) / 64);

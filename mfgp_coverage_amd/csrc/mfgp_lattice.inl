@@ -766,9 +766,14 @@ __device__ __forceinline__ void lat_zunit(const GPDesc& d, int64_t zu, double* s
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const Hyp& h = d.hp;
   const int P = h.kind == 0 ? 1 : 2;
-  const int64_t tabw = d.tabw;   // 64, 128 or 256 (host)
-  const int ZQ = d.zq;           // 2 NT / tabw (<= 8)
+  const int64_t tabw = d.tabw;   // 64, 128, 192 or 256 (host: round_up(max(nx, ny), 64) <= NT)
+  const int ZQ = d.zq;           // 2 NT / tabw, rounded down: 8, 4, 2, 2
   const int ZH = ZQ / 2;         // rows q per thread group
+  // tabw = 192: NT / tabw is no whole number. ZQ = 2, ZH = 1; thread group ql = 0 (192
+  // threads) owns both of the unit's rows; the 64 threads left over (ql = 1, ix < 64) get
+  // rows c ZQ + 1 (again) and c ZQ + 2 (the next unit's: no members here, b = 2 >= ZQ).
+  // Their sums reach the staging buffer past the ZH rows that are stored (the nrow
+  // bound below), so nothing of theirs leaves the unit.
   const int64_t nu = d.nzu / P;
   const int part = (int)(zu / nu);
   const int64_t c = zu % nu;
@@ -956,6 +961,8 @@ __device__ __forceinline__ void lat_zunit(const GPDesc& d, int64_t zu, double* s
     for (int a = 0; a < KA; ++a) zst[(ql * tabw + ix) * KA + a] = acc[hh][a];
     __syncthreads();
     const int64_t q0 = c * ZQ + hh * ZH;   // rows q0 .. q0 + ZH - 1, contiguous in zb
+    // at most ZH rows, those below ny (<= 0 past the last row: nothing stored); at tabw = 192
+    // this also drops the left-over thread group's rows (staged at row ZH and beyond)
     const int64_t nrow = ny - q0 < ZH ? ny - q0 : ZH;
     double* const zr = zb + (part * zrows + q0) * tabw * KA;
     if (d.lat_g2) {
@@ -1187,6 +1194,10 @@ __device__ __forceinline__ void lat_zunit_csr(const GPDesc& d, int64_t zu, doubl
     for (int a = 0; a < KA; ++a) zst[(ql * tabw + ix) * KA + a] = acc[hh][a];
     __syncthreads();
     const int64_t q0 = c * ZQ + hh * ZH;
+    // (tabw = 192: the left-over thread group ql = 1 summed row c ZQ + 1 again and the
+    // next unit's row c ZQ + 2 -- whose list lies past this unit's chunk, so no members;
+    // both are staged past the ZH rows stored here, as in lat_zunit; no stash either:
+    // use_st needs ZQ tabw == 2 NT)
     const int64_t nrow = ny - q0 < ZH ? ny - q0 : ZH;
     double* const zr = zb + (part * zrows + q0) * tabw * KA;
     if (d.lat_g2) {
