@@ -55,8 +55,11 @@ __device__ long long* g_stamps;
                  (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11));                                \
     }                                                                                                \
   } while (0)
-// the lattice step's second launch (k_lat_gemm2/3): its workgroups at role 1024 + tile
-#define WTRACE2(slot)                                                                                \
+// the lattice step's second launch (k_lat_gemm2/3): its workgroups at role 1024 + tile.
+// k_lat_gemm2's slots: 0 start / 1 first ring stage landed / 2 K loop done / 3 the
+// splits' sums stored (barrier) / 6 cells computed / 4 end (thread 0 stamps: the tile's
+// arrival, on the last wave where it goes ahead of the stores, has no stamp)
+#define WTRACE2(slot)                                                                               \
   do {                                                                                               \
     if (threadIdx.x == 0) {                                                                          \
       long long* wt_ = g_stamps + 64 + 8 * ((1024 + blockIdx.y) * gridDim.x + blockIdx.x);                       \
@@ -1763,6 +1766,12 @@ __device__ __forceinline__ void ws_stream(const WsSrc<MODE>& src, int q0, bool a
 // -- the finish's, a wait's timeout -- is drained before its group counts in).
 // Write-through partials, a drain and a relaxed counter: no fence (a release
 // fence writes the whole L2 back).
+// The drain is the calling wave's own (s_waitcnt vmcnt(0)): an arrival says nothing
+// of other waves' stores. The stream kernels call this behind their group's stores.
+// k_lat_gemm2 without status_host calls it on a wave that stores nothing, ahead of
+// its tile's cell stores: there the (max, argmax) and the count are all an arrival
+// carries, and the outputs are visible at the launch's end; with status_host it
+// keeps the order of the stream kernels (lat_gemm2, mfgp_lattice.inl).
 __device__ void var_argmax_group(const GPDesc& d, double bv, int64_t bi, int64_t slot, int64_t nslots) {
   const int lane = threadIdx.x & 63;
   const bool red = d.vmax || d.vargmax;

@@ -1896,17 +1896,30 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MFGP_LAT_WAV
 // The lattice step's GEMM and cells as a second launch (k_lat_gemm2, the default):
 // one 1024-thread workgroup per 64 (a, ix) x 64 iy tile, its K rows split four
 // ways over four groups of four waves -- split s takes the stages s, s + 4, ... of
-// each list, the order of the in-launch split-K at S = 4 -- and the splits' sums
-// meeting in LDS in split order, ((p0 + p1) + p2) + p3, then one cell per thread.
+// each list, the order of the in-launch split-K at S = 4.
 // So no split-K partial goes through memory (64 KB stored and re-read per split
 // tile in the one-launch form: 66 MB per step at B = 8) and no hand-off flag is
 // polled: the kernel boundary orders the Z rows, the L22 record, the new rows'
 // tables and w after the first launch (producers, w units, Z units).
+// The phases of a workgroup, in order:
+//   1. the cells' inputs into LDS (L22 | z2, 1 / L22[a][a], the new rows' tables)
+//      and the old posterior into registers: loads only, no barrier, nothing that
+//      the K loop waits for;
+//   2. the K loop (and a second pass over the virtual rows, if any);
+//   3. every split stores its 64 x 64 sums into the rings' place; one barrier;
+//   4. cells, one per thread: the four sums added in split order,
+//      ((p0 + p1) + p2) + p3, the new V rows, mean and variance, all in registers;
+//   5. the waves' (max, argmax) meet in LDS and the tile counts in on the last wave
+//      (no cell of its own) while the other waves issue the cells' stores -- with
+//      status_host the stores go first and wave 0 counts in, as before.
 // Measured at the headline (B = 8, per-workgroup traces, tools/trace_lat.py): the
 // one-launch form ended at 99-104 us, ~40 us after its last Z unit (K loop under
 // the Z units' flags, the split-K meeting through memory, the cells); the two
-// launches end at ~80 us: the first at ~58, this one ~2 us later and ~20 us long
-// (K loop ~16 us, the splits' meeting ~1.5, the cells ~2).
+// launches end at ~80 us: the first at ~58, this one ~2 us later and ~20 us long.
+// rocprofv3 means of this launch at B = 8: 25.0 us with L22^-1 by forward
+// substitution behind a barrier in phase 1, split 0 adding the sums between two
+// barriers in phase 3, and the tile counted in behind its stores; 24.3 us as above
+// (DESIGN.md 2.4, round 7).
 // ---------------------------------------------------------------------------
 constexpr int G2S = 4;                          // K splits per workgroup
 constexpr int G2NT = 64 * 4 * G2S;              // threads per workgroup
@@ -1917,10 +1930,10 @@ constexpr int G2STG = ZKS * G2R + ZKS * 64;     // doubles per stage: A [8][64] 
 #endif
 constexpr int G2NST = MFGP_G2NST;               // stages in each split's ring
 constexpr int G2RING = G2S * G2NST * G2STG;     // the four rings
-constexpr int G2PARTS = (G2S - 1) * G2R * 64;  // splits 1..3's sums [3][64][64] (in the rings' place)
-static_assert(G2PARTS <= G2RING, "splits 1..3's sums fit the rings' place");
-constexpr int G2EPI = KINC * KINC + KINC + KINC * KINC + 2 * 16 * (4 + 64) + 2 * 16;
-constexpr int G2LDS = G2RING + G2EPI;           // 149 KB
+constexpr int G2PARTS = G2S * G2R * 64;        // the splits' sums [4][64][64] (in the rings' place)
+static_assert(G2PARTS <= G2RING, "the splits' sums fit the rings' place");
+constexpr int G2EPI = KINC * KINC + KINC + KINC + 2 * 16 * (4 + 64) + 2 * 16;
+constexpr int G2LDS = G2RING + G2EPI;           // 147.5 KB
 static_assert(2 * 8 * (8 + 64) <= 2 * 16 * (4 + 64), "both KA's tables fit");
 
 template <int KA, class VT>
@@ -1945,18 +1958,25 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
   const int64_t zq8 = (lat.ny + ZKS - 1) / ZKS * ZKS;
   const int64_t n0 = d.n0;
   double* const L22 = sm + G2RING;                 // [16][16] | z2 [16]
-  double* const Li = L22 + KINC * KINC + KINC;     // L22^-1 [16][16]
-  double* const Fn = Li + KINC * KINC;             // new rows' tables [2][KA][FW]
+  double* const rdi = L22 + KINC * KINC + KINC;    // 1 / L22[a][a] [16]
+  double* const Fn = rdi + KINC;                   // new rows' tables [2][KA][FW]
   double* const amx = Fn + 2 * 16 * (4 + 64);      // the waves' (max, argmax)
   WTRACE2(0);
-  // the cells' inputs (written by the first launch): L22 | z2, the new rows' tables,
-  // then L22^-1 by forward substitution (16 threads). (Issuing the K loop's first
-  // stages before these loads, their latencies overlapped: 92.1-92.7k vs 92.9-93.1k
-  // GP-updates/s without, alternating runs on one box, round 4 -- within noise)
+  // the cells' inputs (written by the first launch): L22 | z2 and the new rows' tables.
+  // Of L22^-1 the cells use the diagonal alone, and the forward substitution that
+  // stood here gave it as 1.0 / L22[a][a] exactly (column a's right-hand side is 1.0
+  // less products with the zeros above the diagonal), so the thread that loads a
+  // diagonal element divides: no barrier, no 16-thread substitution ahead of the
+  // K loop. No barrier here at all: the K loop's come before the cells read this.
+  // (Issuing the K loop's first stages before these loads was slower, not faster:
+  // 77.75 against 76.97 us per step, alternating runs on one box, round 7; stage 0
+  // alone before them, the loads held in registers meanwhile: this launch 24.64
+  // against 24.13 us. Round 4 had measured the first as noise.)
   auto prologue = [&]() {
   for (int e = tid; e < KINC * KINC + KINC; e += G2NT) {
     const bool use = e < KINC * KINC ? (e / KINC < k && e % KINC <= e / KINC) : (e - KINC * KINC < k);
     L22[e] = use ? d.l22r[e] : 0.0;
+    if (e < KINC * KINC && e / KINC == e % KINC) rdi[e / KINC] = use ? 1.0 / L22[e] : 0.0;
   }
   for (int e = tid; e < 2 * KA * FW; e += G2NT) {
     const int kind2 = e / (KA * FW), rem = e % (KA * FW);
@@ -1966,20 +1986,6 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
     const int64_t idx = isx ? ix0 + col : iy0 + (col - IXPT);
     Fn[e] = a < k ? d.tab[t * tstride + (n0 + a) * tabw + idx] : 0.0;
   }
-  __syncthreads();
-  if (tid < KINC) {
-    // column c of L22^-1 by forward substitution
-    const int c = tid;
-    double x[KINC];
-#pragma unroll
-    for (int i = 0; i < KINC; ++i) {
-      double t = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-      for (int b = 0; b < i; ++b) t -= L22[i * KINC + b] * x[b];
-      x[i] = (i < k && i >= c) ? t / L22[i * KINC + i] : 0.0;
-      Li[i * KINC + c] = x[i];
-    }
-  }
   };
   // ---- the K loop: split s, wave w: tile rows 16 w + r, all 64 columns ----
   // Each split streams its stages through its own LDS ring (buffer_load ... lds,
@@ -1987,7 +1993,12 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
   // run in lockstep, a split past its own stages idles). Loading the MFMA operands
   // straight into registers instead (no ring, no barriers) was not faster (K loop
   // 18.3 vs 15.8 us at B = 8): the loop runs at ~34 TF of the ~45 TF a bare f64
-  // MFMA loop reaches with four waves per SIMD.
+  // MFMA loop reaches with four waves per SIMD. Reading stage t + 1's
+  // operands into a second register set ahead of stage t's MFMAs (the barrier then
+  // waits for lgkmcnt(0) too, and a freed slot takes stage t + 4 at once) was not
+  // faster either: this launch 24.28 against 24.33 us with the loop below, round 7 --
+  // with four waves on a SIMD the MFMA pipe already runs one wave's MFMAs beside
+  // another's reads.
   const __amdgpu_buffer_rsrc_t rZ = make_rsrc(d.zb, (int64_t)8 * P * zrows * tabw * KA);
   const __amdgpu_buffer_rsrc_t rAx = make_rsrc(d.axt, (int64_t)8 * 4 * (tabw + 1) * tabw);
   const __amdgpu_buffer_rsrc_t rTab = make_rsrc(d.tab, (int64_t)8 * 4 * tstride);
@@ -2044,6 +2055,7 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
       const int64_t last = hi < t + D ? hi : t + D;
       const int64_t after = last > t + 1 ? last - (t + 1) : 0;
       vm_wait_bar((int)after * CNT);
+      if (t == 0 && slot0 == 0) WTRACE2(1);   // the first stage has landed (every wave's)
       if (t < hi) {
         const double* slot = ring + ((slot0 + t) % G2NST) * G2STG;
         const double* As = slot;
@@ -2086,44 +2098,31 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
   vm_wait_all();
   __syncthreads();   // every ring read is done: the rings become the splits' sums
   WTRACE2(2);
-  // ---- the splits meet: 1..3 store their sums, split 0 adds them in split order ----
+  // ---- the splits meet in the cells: every split stores its sums, one barrier, and
+  // the thread that owns a cell adds its 4 x KA values in split order ----
   // element (16 w + q + 4 v, 16 n + r) of split s's tile is acc[n][v] of its lane
-  double* const Tt = sm;   // the tile's T~ [64][64] (split 1's place, then the sum)
-  if (s > 0) {
-    double* const P_ = sm + (s - 1) * G2R * 64;
+  {
+    double* const P_ = sm + s * G2R * 64;
 #pragma unroll
     for (int n = 0; n < 4; ++n)
 #pragma unroll
       for (int v = 0; v < 4; ++v) P_[(16 * w + q + 4 * v) * 64 + 16 * n + r] = acc[n][v];
   }
   __syncthreads();
-  if (s == 0) {
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int o = (16 * w + q + 4 * v) * 64 + 16 * n + r;
-        double t = acc[n][v] + sm[o];
-        t = t + sm[G2R * 64 + o];
-        t = t + sm[2 * G2R * 64 + o];
-        Tt[o] = t;
-      }
-  }
-  __syncthreads();
   WTRACE2(3);
   // ---- cells: thread t < IXPT x 64 finishes cell (ix0 + t / 64, iy0 + t % 64) ----
   double bv = -__builtin_inf();
   int64_t bi = INT64_MAX;
+  int64_t c = -1;   // this thread's cell (none: -1)
+  double vn[KA];
+  double vc = 0.0, mc = 0.0;
   if (tid < IXPT * 64) {
     const int ixl = tid >> 6, iyl = tid & 63;
     const int64_t ix = ix0 + ixl, iy = iy0 + iyl;
     if (ix < lat.nx && iy < lat.ny) {
-      const int64_t c = ix * lat.sx + iy * lat.sy;
-      const double cov = pcov, com = pcom;
-      VT* const vt = const_cast<VT*>(vres_ptr<VT>(d)) + (c / PBM) * d.vld * PBM + (c % PBM);
-      const double* const Tc = Tt + (ixl * KA) * 64 + iyl;
+      c = ix * lat.sx + iy * lat.sy;
+      const double* const Tc = sm + (ixl * KA) * 64 + iyl;
       const int iyc = IXPT + iyl;
-      double vn[KA];
       double vs = 0.0, ms = 0.0;
 #pragma unroll
       for (int a = 0; a < KA; ++a) {
@@ -2132,31 +2131,51 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
           const double* fL = Fn + a * FW;
           const double* fH = Fn + (KA + a) * FW;
           const double pn = fL[ixl] * fL[iyc] + fH[ixl] * fH[iyc];
-          double t = pn - Tc[a * 64];
+          double tt = Tc[a * 64] + Tc[G2R * 64 + a * 64];
+          tt = tt + Tc[2 * G2R * 64 + a * 64];
+          tt = tt + Tc[3 * G2R * 64 + a * 64];
+          double t = pn - tt;
 #pragma unroll
           for (int b = 0; b < a; ++b) t -= L22[a * KINC + b] * vn[b];
-          vn[a] = t * Li[a * KINC + a];   // 1 / L22[a][a]
+          vn[a] = t * rdi[a];
           vs += vn[a] * vn[a];
           ms += vn[a] * L22[KINC * KINC + a];
-          __hip_atomic_store(vt + (n0 + a) * PBM, (VT)vn[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-      const double vc = cov - vs;
-      const double mc = com + ms;
-      // write-through stores (sc1): the launch leaves no dirty L2 lines for its end
-      // to write back (MI355X_MICROARCH.md: a release writes back the XCD L2s)
-      __hip_atomic_store(d.mu + c, mc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(d.var + c, vc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (d.rmu) {
-        __hip_atomic_store(d.rmu + c, mc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(d.rvar + c, vc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      vc = pcov - vs;
+      mc = pcom + ms;
       argmax_pair(bv, bi, vc, c);
     }
   }
   WTRACE2(6);
+  // write-through stores (sc1): the launch leaves no dirty L2 lines for its end
+  // to write back (MI355X_MICROARCH.md: a release writes back the XCD L2s)
+  auto store_cell = [&]() {
+    if (c < 0) return;
+    VT* const vt = const_cast<VT*>(vres_ptr<VT>(d)) + (c / PBM) * d.vld * PBM + (c % PBM);
+#pragma unroll
+    for (int a = 0; a < KA; ++a)
+      if (a < k) __hip_atomic_store(vt + (n0 + a) * PBM, (VT)vn[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d.mu + c, mc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d.var + c, vc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (d.rmu) {
+      __hip_atomic_store(d.rmu + c, mc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(d.rvar + c, vc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  };
   if (d.vmax || d.vargmax || d.status_host) {
-    // the waves' (max, argmax) meet in LDS in wave order; wave 0 counts the tile in
+    // The tile counts in (var_argmax_group: a store, a returning add and, on the GP's
+    // last tile, a load and a store, each waiting for the one before) ahead of the
+    // cells' stores, on the last wave, which owns no cell: those round trips run
+    // beside the stores' instead of behind them; the launch's end is what makes the
+    // outputs visible. Not with status_host (the eager one-GP call): whoever polls
+    // that word may take it for the outputs, so there the tile counts in behind its
+    // stores, on wave 0, as it always did.
+    const bool ahead = d.status_host == nullptr;
+    const int aw = ahead ? G2NT / 64 - 1 : 0;
+    static_assert(IXPT * 64 <= G2NT - 64, "the last wave owns no cell");
+    if (!ahead) store_cell();
+    // the waves' (max, argmax) meet in LDS in wave order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) argmax_pair(bv, bi, __shfl_xor(bv, off), __shfl_xor(bi, off));
     int64_t* const ami = reinterpret_cast<int64_t*>(amx);
@@ -2165,12 +2184,15 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
       ami[2 * wg + 1] = bi;
     }
     __syncthreads();
-    if (wg == 0) {
+    if (wg == aw) {
       bv = amx[0];
       bi = ami[1];
       for (int ww = 1; ww < G2NT / 64; ++ww) argmax_pair(bv, bi, amx[2 * ww], ami[2 * ww + 1]);
       var_argmax_group(d, bv, bi, tile, d.lat_tiles);
     }
+    if (ahead) store_cell();
+  } else {
+    store_cell();
   }
   WTRACE2(4);
 }

@@ -82,7 +82,8 @@ def main(d, tag, pre="bench"):
         m.to_csv(f"profiles/{tag}_mfma_util.csv", index=False)
         print(m.to_string())
     with open(f"profiles/{tag}_build.json", "w") as f:
-        json.dump({"tag": tag, "src_sha": source_sha(), "profile_dir": d}, f)
+        # (the directory's own name: where it lay during the run says nothing later)
+        json.dump({"tag": tag, "src_sha": source_sha(), "profile_dir": os.path.basename(os.path.normpath(d))}, f)
     print(s.head(8).to_string())
 
 

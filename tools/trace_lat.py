@@ -2,7 +2,9 @@
 Slots: producers 0 start / 1 arrival / 4 end; w blocks 0 start / 1 past the L21 wait / 3 F loop done /
 2 published; Z units 0 start / 1 scanned / 3 past the w wait / 2 published; GEMM 0 start / 1 past
 the Z wait / 2 K loop done / 3 past the
-L22 wait (reducers) / 5 new-row factors and L22^-1 done / 6 cells done / 4 end. Launches back to back; the trace is the last launch's."""
+L22 wait (reducers) / 5 new-row factors and L22^-1 done / 6 cells done / 4 end; k_lat_gemm2 (roles 1024 + tile):
+0 start / 1 first ring stage landed / 2 K loop done / 3 the splits' sums stored (barrier) / 6 cells computed /
+4 end (cells stored, tile counted in). Launches back to back; the trace is the last launch's."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["MFGP_LIB"] = sys.argv[1]
@@ -73,7 +75,7 @@ print(f"B={B} ({nwu} w units, {nzu} Z units per GP): percentiles 0/10/50/90/100 
 for name, sel, slots in (("producer", role < nprod, (0, 1, 4)), ("w unit", (role >= nprod) & (role < nprod + nwu), (0, 1, 3, 2)),
                          ("Z unit", (role >= nprod + nwu) & (role < nprod + nwu + nzu), (0, 1, 3, 4, 5, 6, 2)),
                          ("gemm", ((role >= 1024) if G2 else (role >= nprod + nwu + nzu)) & used,
-                          (0, 2, 3, 6, 4) if G2 else (0, 1, 2, 3, 5, 6, 4))):
+                          (0, 1, 2, 3, 6, 4) if G2 else (0, 1, 2, 3, 5, 6, 4))):
     for sl in slots:
         print(f"  {name:9s} slot {sl}: {q(tr[sel, sl])}")
 gm = ((role >= 1024) if G2 else (role >= nprod + nwu + nzu)) & used
@@ -81,6 +83,10 @@ w = tr[(role >= nprod) & (role < nprod + nwu)]
 print(f"  w units published (slot 2, last arrivers): {q(w[:, 2])}")
 print(f"  w unit F loop (slot 3 - slot 1): {q(w[:, 3] - w[:, 1])}; reduce+publish (2 - 3): {q(w[:, 2] - w[:, 3])}")
 print(f"  gemm K-loop durations (slot2 - slot1): {q(tr[gm, 2] - tr[gm, 1])}")
+if G2:
+    g2 = tr[gm]
+    print(f"  gemm2: start to first stage (1 - 0) {q(g2[:, 1] - g2[:, 0])}; K done to sums stored (3 - 2) {q(g2[:, 3] - g2[:, 2])}; "
+          f"cells (6 - 3) {q(g2[:, 6] - g2[:, 3])}; stores and arrival (4 - 6) {q(g2[:, 4] - g2[:, 6])}; whole (4 - 0) {q(g2[:, 4] - g2[:, 0])}")
 red = gm & np.isfinite(tr[:, 3])
 print(f"  reducers: reduce+L22 wait (3 - 2) {q(tr[red, 3] - tr[red, 2])}; Fn/Li (5 - 3) {q(tr[red, 5] - tr[red, 3])}; "
       f"cells (6 - 5) {q(tr[red, 6] - tr[red, 5])}; argmax (4 - 6) {q(tr[red, 4] - tr[red, 6])}")
