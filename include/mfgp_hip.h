@@ -31,6 +31,7 @@ extern "C" {
 #define MFGP_ERR_NOT_PD 1   /* Cholesky pivot <= 0: numpy.linalg.LinAlgError (gp:254, gp:529) */
 #define MFGP_ERR_ARG 2      /* bad argument: TypeError/ValueError (simulator.py:366, 652)     */
 #define MFGP_ERR_DEVICE 3   /* HIP runtime error: RuntimeError                                */
+#define MFGP_ERR_NO_V 4     /* mfgp_cov_block: the resident V does not cover the model's rows   */
 
 #define MFGP_SF 0           /* SFGP, gaussian_process.py:23-268, hyp [mu, s2, L, noise]              */
 #define MFGP_MF 1           /* MFGP, gaussian_process.py:271-578, hyp [mu_lo,s2_lo,L_lo,mu_hi,s2_hi,
@@ -184,6 +185,35 @@ int mfgp_release_view(void* view);
  * *valid = 0 (a predict without an append before it). Read after the buffer is
  * ready (mfgp_predict_view_running: after mfgp_ctx_synchronize). */
 int mfgp_view_max(const void* view, double* vmax, int64_t* argmax, int* valid);
+
+/* A block of the dense posterior covariance that predict returns in the
+ * reference (gp:146 / gp:435-436): out[i * ldo + j] = cov(x_rows[i], x_cols[j]) =
+ * k**(x_i, x_j) - sum_n V[n, i] V[n, j] over the model's N training rows, from the
+ * resident V = L^-1 psi^T (k_cov_block: one f64-MFMA GEMM over V's rows plus the
+ * prior term; no M x M intermediate). rows / cols: host arrays of grid cell
+ * indices in [0, M), in any order, repeats allowed; NULL = all cells 0..M-1 (then
+ * na / nb must equal M). out: host or device memory, row-major with leading
+ * dimension ldo >= nb. flags: MFGP_COV_PRIOR = the prior covariance k** alone (no
+ * factor needed). The call first brings the model to the state mfgp_predict leaves
+ * (a pending or deferred append, new hyperparameters or a new grid run their
+ * factor and predict here, and MFGP_ERR_NOT_PD surfaces as there); if V still
+ * does not cover the N rows it returns MFGP_ERR_NO_V. Every index is validated
+ * before anything is enqueued: an index outside [0, M), ldo < nb or a model
+ * without a grid returns MFGP_ERR_ARG, launches nothing and leaves the model as
+ * it was. na == 0 or nb == 0: MFGP_OK, nothing written. MFGP_F32 models:
+ * MFGP_ERR_ARG (their fp32 V needs its own tolerance policy). An entry's bits
+ * depend only on its pair of cells: block(a, b) == block(b, a)^T, any block
+ * equals the same entries of the full matrix, and two calls agree bit for bit. */
+#define MFGP_COV_PRIOR 1
+int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
+                   double* out, int64_t ldo, int flags);
+/* The model's posterior serial: a value that changes whenever its training rows,
+ * hyperparameters, jitter or grid change (appends, the batch entry points,
+ * mfgp_truncate, mfgp_set_data / _set_hyp / _set_grid, the planners' loops), and is
+ * never reused within the process -- truncate followed by an append of the same
+ * count gives a new one. What a holder of an earlier result compares to know
+ * whether the model still holds that posterior. No device work. */
+int mfgp_model_serial(const mfgp_model* m, uint64_t* serial);
 
 /* Sizes and state readers (the Python mirror's .X/.L attributes). */
 int64_t mfgp_model_n(const mfgp_model* m);      /* N = NL + NH */

@@ -14,7 +14,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFGP_LIB") or os.path.join(HERE, "libmfgp_hip.so")
 
-OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE = 0, 1, 2, 3
+OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE, ERR_NO_V = 0, 1, 2, 3, 4
+COV_PRIOR = 1
 SF, MF = 0, 1
 F64, F32 = 0, 1
 ASYNC = 1
@@ -71,6 +72,9 @@ SIGNATURES = {
     "mfgp_predict_view_running": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                                  ctypes.POINTER(ctypes.c_int)]),
+    "mfgp_cov_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "mfgp_model_serial": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "mfgp_release_view": (ctypes.c_int, [ctypes.c_void_p]),
     "mfgp_view_max": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_int64_p, ctypes.POINTER(ctypes.c_int)]),
     "mfgp_model_n": (ctypes.c_int64, [ctypes.c_void_p]),
@@ -358,6 +362,51 @@ class Model:
         vm, am, ok = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int(0)
         check(L.mfgp_view_max(ctypes.c_void_p(view.value), ctypes.byref(vm), ctypes.byref(am), ctypes.byref(ok)))
         return mu, var, ((np.float64(vm.value), int(am.value)) if ok.value else None)
+
+    def cov_block(self, rows=None, cols=None, out=None, prior=False, ldo=None):
+        """cov[rows, cols] of the dense posterior covariance (gp:146 / gp:435-436) from the
+        resident V (mfgp_cov_block): an [a, b] ndarray. rows / cols: sequences of grid
+        cell indices in [0, M) (any order, repeats allowed), None = all cells. out: a host
+        float64 matrix to fill in place (its row stride is the leading dimension), or the
+        integer device address of a row-major [a, ldo] float64 buffer (ldo defaults to b;
+        returns None). prior: the prior covariance k** alone.
+        Settles a pending append / new hyperparameters / a new grid as predict() would."""
+        L = lib()
+        M = L.mfgp_model_m(self.handle)
+
+        def lst(v):
+            if v is None:
+                return None, M
+            a = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.int64)
+            return a, a.shape[0]
+        r, na = lst(rows)
+        c, nb = lst(cols)
+        flags = COV_PRIOR if prior else 0
+
+        def ip(a):   # (an empty list is still a list: a non-null pointer)
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+        if isinstance(out, np.ndarray):
+            # a caller's host matrix: row-major float64 rows, leading dimension = its row stride
+            if out.dtype != np.float64 or out.ndim != 2 or out.strides[1] != 8 or out.strides[0] % 8 or \
+                    out.shape[0] < na or not out.flags.writeable:
+                raise ValueError("out must be a writable row-major float64 matrix of at least [a] rows")
+            check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(out.ctypes.data),
+                                   int(out.strides[0] // 8 if ldo is None else ldo), flags))
+            return out[:na, :nb]
+        if out is not None:
+            check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(int(out)),
+                                   int(nb if ldo is None else ldo), flags))
+            return None
+        buf = np.empty((na, nb), dtype=np.float64)
+        check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(buf.ctypes.data), nb, flags))
+        return buf
+
+    def serial(self):
+        """The model's posterior serial (mfgp_model_serial): changes whenever its rows,
+        hyperparameters, jitter or grid change, and never repeats."""
+        v = ctypes.c_uint64(0)
+        check(lib().mfgp_model_serial(self.handle, ctypes.byref(v)))
+        return int(v.value)
 
     def factor(self):
         n = lib().mfgp_model_n(self.handle)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -228,6 +229,11 @@ struct mfgp_model {
   // state generation: a new factor from scratch, a new grid or new hyperparameters
   // start a new one (the resident posterior, F and the tables belong to one)
   uint64_t gen = 1;
+  // posterior serial (mfgp_model_serial): a process-wide fresh value at every change
+  // of the rows, hyperparameters, jitter or grid -- unlike (gen, N) it never repeats
+  // (truncate + append of the same count), so a holder of an earlier predict's
+  // result can tell whether the model still holds that posterior
+  uint64_t serial = 0;
   // resident posterior: two buffers [mu | var] of M each, written by every predict
   // (incremental mode); buffer b holds the posterior of the res_n[b] leading rows
   double* res = nullptr;
@@ -267,6 +273,9 @@ struct mfgp_model {
 };
 
 namespace {
+
+std::atomic<uint64_t> g_serial{0};
+void bump_serial(mfgp_model* m) { m->serial = g_serial.fetch_add(1, std::memory_order_relaxed) + 1; }
 
 Hyp derive_hyp(int kind, const double* hyp, double jitter) {
   Hyp h{};
@@ -1606,6 +1615,7 @@ int mfgp_model_create(mfgp_ctx* c, int kind, int dtype, const double* hyp, int n
   m->nhyp = nhyp;
   std::memcpy(m->hyp, hyp, sizeof(double) * nhyp);
   m->jitter = jitter;
+  bump_serial(m);
   HIP_TRY(hipMalloc(&m->status, sizeof(int)));
   {
     // "no failure" until a step writes it: a step whose kernels all skip (a gated
@@ -1719,6 +1729,7 @@ int mfgp_model_set_hyp(mfgp_model* m, const double* hyp, int nhyp, double jitter
   if (jitter != m->jitter || std::memcmp(hyp, m->hyp, sizeof(double) * nhyp) != 0) {
     m->spec_valid = false;
     m->gen += 1;
+    bump_serial(m);
   }
   std::memcpy(m->hyp, hyp, sizeof(double) * nhyp);
   m->jitter = jitter;
@@ -1777,6 +1788,7 @@ int mfgp_set_grid(mfgp_model* m, const double* xs, int64_t M) {
   m->v_n = 0;   // V columns belong to the previous grid
   m->spec_valid = false;
   m->gen += 1;
+  bump_serial(m);
   if (M > m->Mcap) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (m->grid) HIP_TRY(hipFree(m->grid));
@@ -1805,6 +1817,7 @@ int mfgp_set_data(mfgp_model* m, const double* XL, const double* yL, int64_t NL,
   if (NL < 0 || NH < 0) return set_err(MFGP_ERR_ARG, "negative sizes");
   if (m->kind == MFGP_SF && NL != 0) return set_err(MFGP_ERR_ARG, "SF model takes its data in the H slots");
   m->spec_valid = false;
+  bump_serial(m);
   if ((rc = ensure_cap(m, NL + NH))) return rc;
   m->NL = NL;
   m->NH = NH;
@@ -1823,6 +1836,7 @@ int mfgp_append(mfgp_model* m, const double* X, const double* y, int64_t k) {
   if (rc) return rc;
   if (k < 0) return set_err(MFGP_ERR_ARG, "negative k");
   m->spec_valid = false;
+  if (k > 0) bump_serial(m);
   const bool spec = m->pred_since_append;   // the last append was followed by a predict
   m->pred_since_append = false;
   const int64_t n = m->NL + m->NH;
@@ -1851,6 +1865,7 @@ int mfgp_truncate(mfgp_model* m, int64_t n_keep_hifi) {
   if (n_keep_hifi < 0 || n_keep_hifi > m->NH) return set_err(MFGP_ERR_ARG, "bad truncate size");
   if (n_keep_hifi != m->NH) {
     m->NH = n_keep_hifi;
+    bump_serial(m);
     // the factor, z and V of the leading rows do not depend on later rows
     const int64_t N = m->NL + m->NH;
     if (m->factored && m->factor_N > N) m->factor_N = N;
@@ -2053,6 +2068,78 @@ int mfgp_predict(mfgp_model* m, double* mu, double* var) {
   return MFGP_OK;
 }
 
+// V holds all N rows of the current factor, hyperparameters and grid: the state
+// every predict path leaves (mfgp_cov_block reads rows [0, N) of it).
+static bool v_covers(const mfgp_model* m) {
+  return factor_current(m) && m->V && m->v_n == m->NL + m->NH && m->vtiles >= ntiles_grid(m->M);
+}
+
+int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb, double* out,
+                   int64_t ldo, int flags) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  mfgp_ctx* c = m->ctx;
+  if (m->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_block: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
+  if (m->M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: the model has no grid (mfgp_set_grid)");
+  if (na < 0 || nb < 0) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: negative block size");
+  if ((!rows && na != m->M) || (!cols && nb != m->M))
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_block: a NULL index list means all %lld cells (got na = %lld, nb = %lld)",
+                   (long long)m->M, (long long)na, (long long)nb);
+  if (na == 0 || nb == 0) return MFGP_OK;
+  if (!out) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: null output");
+  if (ldo < nb)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_block: ldo = %lld is less than nb = %lld", (long long)ldo, (long long)nb);
+  if ((na + 63) / 64 > 65535) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: at most %d rows per call", 65535 * 64);
+  for (int s = 0; s < 2; ++s) {
+    const int64_t* l = s ? cols : rows;
+    const int64_t n = s ? nb : na;
+    for (int64_t i = 0; l && i < n; ++i)
+      if (l[i] < 0 || l[i] >= m->M)
+        return set_err(MFGP_ERR_ARG, "mfgp_cov_block: %s[%lld] = %lld is outside the grid's cells [0, %lld)",
+                       s ? "cols" : "rows", (long long)i, (long long)l[i], (long long)m->M);
+  }
+  const bool prior = (flags & MFGP_COV_PRIOR) != 0;
+  if (!prior && m->NL + m->NH > 0 && !v_covers(m)) {
+    // as mfgp_predict would (a pending or deferred append, new hyperparameters, a
+    // new grid): into the model's result buffer, kept for the next predict
+    if ((rc = ensure_spec_out(m))) return rc;
+    m->spec_valid = false;   // (a kept result without its V is of no use here: recompute)
+    if ((rc = mfgp_predict(m, m->spec_out, m->spec_out + m->spec_cap))) return rc;
+    if (!v_covers(m))
+      return set_err(MFGP_ERR_NO_V, "mfgp_cov_block: the resident V holds %lld of the model's %lld rows after a predict",
+                     (long long)m->v_n, (long long)(m->NL + m->NH));
+  }
+  // workspace: [rows | cols | the block, when out is host memory]
+  const bool host = !is_device_ptr(out);
+  const size_t ib = sizeof(int64_t) * (size_t)((rows ? na : 0) + (cols ? nb : 0));
+  const size_t ioff = (ib + 255) / 256 * 256;
+  if ((rc = ensure_ws(c, ioff + (host ? sizeof(double) * (size_t)na * nb : 0)))) return rc;
+  char* ws = reinterpret_cast<char*>(c->ws);
+  int64_t* drows = rows ? reinterpret_cast<int64_t*>(ws) : nullptr;
+  int64_t* dcols = cols ? reinterpret_cast<int64_t*>(ws) + (rows ? na : 0) : nullptr;
+  if (rows) HIP_TRY(hipMemcpyAsync(drows, rows, sizeof(int64_t) * na, hipMemcpyHostToDevice, c->stream));
+  if (cols) HIP_TRY(hipMemcpyAsync(dcols, cols, sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
+  double* kout = host ? reinterpret_cast<double*>(ws + ioff) : out;
+  const int64_t kld = host ? nb : ldo;
+  GPDesc d;
+  fill_desc(d, m);
+  HIP_TRY(launch_cov_block(d, drows, na, dcols, nb, kout, kld, (prior || d.N == 0) ? 1 : 0, c->stream));
+  if (host)
+    HIP_TRY(hipMemcpy2DAsync(out, sizeof(double) * ldo, kout, sizeof(double) * nb, sizeof(double) * nb, na,
+                             hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MFGP_OK;
+}
+
+int mfgp_model_serial(const mfgp_model* m, uint64_t* serial) {
+  if (!m || !serial) return set_err(MFGP_ERR_ARG, "null model/out");
+  *serial = m->serial;
+  return MFGP_OK;
+}
+
 int64_t mfgp_model_n(const mfgp_model* m) { return m ? m->NL + m->NH : -1; }
 
 int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n) {
@@ -2176,7 +2263,10 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
     src_off[i] = off;
     // host rows: the bordered appends carry them in their descriptors (rows_inline,
     // landed by the producers); the others are copied below, before their launches
-    if (ki > 0) m->NH += ki;
+    if (ki > 0) {
+      m->NH += ki;
+      bump_serial(m);
+    }
     off += ki;
     if (!c->incremental) m->factored = false;   // reference behaviour: refactor every update
   }
@@ -2547,6 +2637,7 @@ static size_t plan_res_doubles(const mfgp_model* m) { return m->res ? 4 * (size_
 // save what the loop may overwrite; `room` (plan_res_doubles) receives the posterior
 static int plan_enter(mfgp_model* m, PlanSave& s, double* room) {
   s.NH0 = m->NH;
+  bump_serial(m);   // the loop appends in place: no earlier result's holder may read V meanwhile
   s.res = (m->res && room) ? room : nullptr;
   if (s.res) HIP_TRY(hipMemcpyAsync(s.res, m->res, sizeof(double) * 4 * m->res_M, hipMemcpyDeviceToDevice, m->ctx->stream));
   for (int b = 0; b < 2; ++b) {
@@ -2599,6 +2690,7 @@ static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   m->n_post_copy = s.cnt[7];
   m->n_early_pd = s.cnt[8];
   m->NH = s.NH0;
+  bump_serial(m);
   const int64_t N = m->NL + m->NH;
   // the factor of the model's own rows is the one it entered with (the loop wrote
   // rows past them only, also in a step that failed); V likewise, and what the loop's

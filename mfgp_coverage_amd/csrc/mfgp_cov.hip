@@ -1,0 +1,147 @@
+// Blocks of the dense posterior covariance for gfx950 (MI355X), fp64.
+//
+// Reference: SFGP.predict / MFGP.predict return the dense [M,M] covariance
+// (gaussian_process.py:146, 435-436):
+//   cov = k**(X*, X*) - psi K^-1 psi^T = k**(X*, X*) - V^T V,   V = L^-1 psi^T
+// V is resident per model after every predict path ([tile][vld][64 cells], rows
+// [0, N) valid), so a block cov[rows, cols] is one GEMM over V's rows plus the
+// prior term:
+//   k_cov_block   one workgroup per 64x64 output tile, four waves of 32x32 on
+//                 v_mfma_f64_16x16x4; K loop over the training rows in chunks of
+//                 64, both operand panels gathered through LDS (lane -> cell, so
+//                 a contiguous index list reads V's 512-byte rows whole)
+// Every output entry accumulates the products V[n,i] V[n,j] in the same order
+// (n ascending, no split-K, no atomics) whatever its place in a tile, so an
+// entry's bits depend only on its pair of cells: block(a, b) == block(b, a)^T
+// and any sub-block equals the same entries of the full matrix, bit for bit.
+#include <hip/hip_runtime.h>
+
+#include "mfgp_device.h"
+#include "mfgp_internal.h"
+
+namespace mfgp {
+
+constexpr int CKC = NB;            // training rows per K chunk (tile_mma's depth)
+constexpr int CPT = CKC * 64 / NT; // panel elements per thread and chunk (16)
+
+// One chunk of both operand panels in registers (issue-early / write-late): the
+// loads of chunk c + 1 are in flight while the MFMAs of chunk c run.
+struct CovStage {
+  double a[CPT], b[CPT];
+};
+
+// Thread (wave w, lane) stages cell `lane` of either panel, rows n0 + 4 p + w.
+// pa / pb: the cell's column of V (row n at [n * 64]); rows >= N and cells past
+// the lists are zeros and are never loaded (V's rows past N may hold an older
+// model's values, its tiles' cells past M nothing).
+__device__ __forceinline__ void cov_fetch(CovStage& st, const GLOBAL double* pa, const GLOBAL double* pb,
+                                          bool oka, bool okb, int64_t n0, int64_t N, int w) {
+#pragma unroll
+  for (int p = 0; p < CPT; ++p) {
+    const int64_t n = n0 + 4 * p + w;
+    const bool in = n < N;
+    st.a[p] = (in && oka) ? pa[n * PBM] : 0.0;
+    st.b[p] = (in && okb) ? pb[n * PBM] : 0.0;
+  }
+}
+
+// As[swz(k, i)] = V[n0 + k][row cell i], Bs[swz(k, j)] = V[n0 + k][column cell j]
+__device__ __forceinline__ void cov_put(double* __restrict__ As, double* __restrict__ Bs, const CovStage& st,
+                                        int w, int lane) {
+#pragma unroll
+  for (int p = 0; p < CPT; ++p) {
+    const int k = 4 * p + w;
+    As[swz(k, lane)] = st.a[p];
+    Bs[swz(k, lane)] = st.b[p];
+  }
+}
+
+// A cell's coordinates over both length scales (x / l, as the reference scales
+// before it subtracts, gp:77-78).
+struct CovPt {
+  double xL, yL, xH, yH;
+};
+__device__ __forceinline__ CovPt cov_pt(const Hyp& h, const double* __restrict__ grid, int64_t cell) {
+  const double x = gp(grid)[2 * cell], y = gp(grid)[2 * cell + 1];
+  CovPt p;
+  p.xL = div_(x, h.lL);
+  p.yL = div_(y, h.lL);
+  p.xH = div_(x, h.lH);
+  p.yH = div_(y, h.lH);
+  return p;
+}
+
+// k**(x_i, x_j) (gp:146 SF: s k; gp:435-436 MF: rho^2 s_L k_L + s_H k_H) minus the
+// accumulated V_i . V_j, no FMA contraction.
+__device__ __forceinline__ double cov_entry(const Hyp& h, const CovPt& a, const CovPt& b, double vv) {
+#pragma clang fp contract(off)
+  const double kl = se_scaled(a.xL, a.yL, b.xL, b.yL, h.sL);
+  double kss = kl;
+  if (h.kind != 0) {
+    const double kh = se_scaled(a.xH, a.yH, b.xH, b.yH, h.sH);
+    kss = h.rho2 * kl + kh;
+  }
+  return kss - vv;
+}
+
+// out[i * ldo + j] = cov(rows[i], cols[j]), i < na, j < nb; rows / cols null = the
+// identity list. Grid: (ceil(nb / 64), ceil(na / 64)). prior_only: k** alone.
+__global__ __launch_bounds__(NT) void k_cov_block(const GPDesc d, const int64_t* __restrict__ rows, int64_t na,
+                                                  const int64_t* __restrict__ cols, int64_t nb,
+                                                  double* __restrict__ out, int64_t ldo, int prior_only) {
+  __shared__ double As[TILE];
+  __shared__ double Bs[TILE];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wm = w >> 1, wn = w & 1;
+  const int64_t i0 = (int64_t)blockIdx.y * 64, j0 = (int64_t)blockIdx.x * 64;
+  const int64_t N = prior_only ? 0 : d.N;
+  Acc acc;
+  acc_zero(acc);
+  if (N > 0) {
+    const bool oka = i0 + lane < na, okb = j0 + lane < nb;
+    const int64_t ca = oka ? (rows ? gp(rows)[i0 + lane] : i0 + lane) : 0;
+    const int64_t cb = okb ? (cols ? gp(cols)[j0 + lane] : j0 + lane) : 0;
+    const GLOBAL double* pa = gp(d.V) + (ca / PBM) * d.vld * PBM + ca % PBM;
+    const GLOBAL double* pb = gp(d.V) + (cb / PBM) * d.vld * PBM + cb % PBM;
+    CovStage st;
+    cov_fetch(st, pa, pb, oka, okb, 0, N, w);
+    for (int64_t n0 = 0; n0 < N; n0 += CKC) {
+      cov_put(As, Bs, st, w, lane);
+      __syncthreads();
+      if (n0 + CKC < N) cov_fetch(st, pa, pb, oka, okb, n0 + CKC, N, w);
+      tile_mma<false>(As, Bs, acc, wm, wn, lane);
+      __syncthreads();
+    }
+  }
+  const Hyp& h = d.hp;
+  const int r = lane & 15, q = lane >> 4;
+  CovPt pc[2];
+  int64_t jc[2];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+    jc[nt] = j0 + acc_col(wn, nt, r);
+    const int64_t cell = jc[nt] < nb ? (cols ? gp(cols)[jc[nt]] : jc[nt]) : 0;
+    pc[nt] = cov_pt(h, d.grid, cell);
+  }
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int64_t i = i0 + acc_row(wm, mt, q, v);
+      if (i >= na) continue;
+      const CovPt pr = cov_pt(h, d.grid, rows ? gp(rows)[i] : i);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+        if (jc[nt] < nb) gp(out)[i * ldo + jc[nt]] = cov_entry(h, pr, pc[nt], acc.c[mt][nt][v]);
+    }
+}
+
+hipError_t launch_cov_block(const GPDesc& d, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
+                            double* out, int64_t ldo, int prior_only, hipStream_t s) {
+  if (na <= 0 || nb <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((nb + 63) / 64), (unsigned)((na + 63) / 64));
+  hipLaunchKernelGGL(k_cov_block, grid, dim3(NT), 0, s, d, rows, na, cols, nb, out, ldo, prior_only);
+  return hipGetLastError();
+}
+
+}  // namespace mfgp

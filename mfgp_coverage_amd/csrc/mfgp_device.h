@@ -1,5 +1,5 @@
 // Device-side helpers shared by the HIP translation units of libmfgp_hip.so
-// (mfgp_kernels.hip, mfgp_nlml.hip): f64 MFMA tile products, LDS tile staging,
+// (mfgp_kernels.hip, mfgp_nlml.hip, mfgp_cov.hip): f64 MFMA tile products, LDS tile staging,
 // the SE kernel in the reference's operation order (gaussian_process.py:66-79)
 // and the K entries of gp:253-254 / gp:523-529.
 #pragma once

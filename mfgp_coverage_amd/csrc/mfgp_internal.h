@@ -255,6 +255,12 @@ struct PostArg {
   PostCopy p[POST_MAX];
 };
 hipError_t launch_post_copy(const PostCopy* h, int count, hipStream_t s);
+// a block of the dense posterior covariance from the resident V (k_cov_block,
+// mfgp_cov.hip): out[i * ldo + j] = k**(rows[i], cols[j]) - sum_n V[n, rows[i]] V[n, cols[j]],
+// n < d.N; rows / cols: device lists of cells in [0, M), or null = 0..M-1 (then
+// na / nb = M); prior_only: the k** term alone. Descriptor by value.
+hipError_t launch_cov_block(const GPDesc& d, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
+                            double* out, int64_t ldo, int prior_only, hipStream_t s);
 hipError_t launch_nlml_value(const GPDesc* d, int count, double* out, hipStream_t s);
 hipError_t launch_nlml_grad(const GPDesc* d, int64_t N, double* Xi, double* Kv, double* alpha, double* part,
                             hipStream_t s);

@@ -15,14 +15,22 @@ Differences from the reference, all on the output side of the contract:
   (``np.diag`` at simulator.py:301, 341, 685, 855; ``np.amax`` at 672, 842,
   1014; plotter.py:160). ``np.diag``/``np.amax``/``np.argmax`` of it give what
   they give on the dense matrix (for a PSD covariance the maximum entry lies on
-  the diagonal); any other use materialises it only when M == 1.
+  the diagonal). The off-diagonal entries are computed on demand from the V the
+  device keeps (k_cov_block): ``cov[i, j]``, slices and ``cov.block(rows, cols)``
+  take one block without forming M x M; ``np.asarray(cov)``, ``np.linalg.*`` and
+  arithmetic materialise the dense matrix once (up to ``DiagCov.DENSE_MAX_BYTES``).
+  A covariance whose model has since been updated raises RuntimeError off the
+  diagonal. ``precision = "f32"`` models keep the diagonal only.
 * The factorisation is the GPU's; results agree with the reference to the
   tolerance in oracle/gp_oracle.py (mu rel 1e-6, var rel 1e-6 floored at
   1e-6 * k**).
 * ``likelihood``/``train`` (gp:81-119, 344-399) run on the GPU with an analytic
-  gradient in place of autograd (``likelihood_and_grad``). The unused extras
-  (``ExpectedImprovement``, ``draw_*``, ``pred_var``, ``get_*_var``) are out of
-  scope of this engine.
+  gradient in place of autograd (``likelihood_and_grad``).
+* ``draw_prior_samples`` / ``draw_posterior_samples`` (gp:180-217) draw from the
+  device's covariance; the posterior draws are of ``predict``'s posterior (the
+  reference's omit the prior mean and do not centre y). The other unused extras
+  (``ExpectedImprovement``, ``pred_var``, ``get_*_var``) are out of scope of
+  this engine.
 """
 from __future__ import annotations
 
@@ -34,19 +42,36 @@ from . import _lib
 
 
 class DiagCov:
-    """Diagonal-only stand-in for the dense [M,M] posterior covariance of gp:146 / gp:435-436.
+    """The posterior covariance of gp:146 / gp:435-436: its diagonal held, the rest on demand.
 
-    fused: (max, first argmax) of ``var`` as the launch that computed it reduced them
-    (the eager append's epilogue, mfgp_view_max), or None: then ``np.amax`` /
-    ``np.argmax`` return it instead of rescanning the M-vector on the host. The
-    maximum of a vector is exact, so the value is the host scan's bit for bit
-    (tests/test_boundary.py)."""
+    var: the diagonal, as the predict computed it. fused: (max, first argmax) of
+    ``var`` as the launch that computed it reduced them (the eager append's epilogue,
+    mfgp_view_max), or None: then ``np.amax`` / ``np.argmax`` return it instead of
+    rescanning the M-vector on the host. The maximum of a vector is exact, so the
+    value is the host scan's bit for bit (tests/test_boundary.py).
 
-    __slots__ = ("var", "fused")
+    source / serial: the device model (``_lib.Model``: ``cov_block``, ``serial``) whose
+    resident V holds this posterior, and its posterior serial at predict time. With
+    them the off-diagonal entries are computed when asked for (k_cov_block):
+    ``block(rows, cols)``, ``cov[i, j]`` and any pair of ints / slices take one block
+    call without forming the matrix; every other use (``np.asarray``, ufuncs, linalg,
+    arithmetic) materialises the dense matrix once and keeps it, up to
+    ``DENSE_MAX_BYTES``. Once the model has moved on (its serial changed: an update,
+    new hyperparameters, another grid) such an access raises RuntimeError -- the V
+    it would read belongs to another posterior. The diagonal (``np.diag``,
+    ``np.amax``, ``np.argmax``, ``np.trace``, ``cov[i, i]``) stays ``var`` throughout.
+    Without a source (as before): only the diagonal, anything else raises TypeError."""
 
-    def __init__(self, var, fused=None):
+    __slots__ = ("var", "fused", "source", "serial", "_cache")
+
+    DENSE_MAX_BYTES = 1 << 30
+
+    def __init__(self, var, fused=None, source=None, serial=None):
         self.var = np.asarray(var, dtype=np.float64).reshape(-1)
         self.fused = fused
+        self.source = source
+        self.serial = (source.serial() if serial is None else serial) if source is not None else None
+        self._cache = None
 
     @property
     def shape(self):
@@ -61,22 +86,82 @@ class DiagCov:
     def __len__(self):
         return self.var.shape[0]
 
+    def _live(self):
+        """The source model, checked to hold this posterior still."""
+        if self.source is None:
+            raise TypeError("DiagCov holds only the diagonal of the posterior covariance (the off-diagonal "
+                            "entries are never computed); use np.diag(cov) / np.amax(cov)")
+        if self.source.serial() != self.serial:
+            raise RuntimeError("the model has been updated since this predict (its data, hyperparameters or grid "
+                               "changed): the off-diagonal covariance of the earlier posterior is gone; "
+                               "np.diag(cov) still holds its diagonal")
+        return self.source
+
+    def _cells(self, sel):
+        """An index list for one axis: None (all cells) or an int64 array in [0, M)."""
+        M = self.var.shape[0]
+        if sel is None:
+            return None
+        if isinstance(sel, slice):
+            return np.arange(*sel.indices(M), dtype=np.int64)
+        a = np.asarray(sel)
+        if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+            if a.size:
+                raise IndexError("cell indices must be integers")
+            a = a.astype(np.int64)
+        a = a.astype(np.int64).reshape(-1)
+        if a.size and (a.min() < -M or a.max() >= M):
+            raise IndexError(f"cell index out of range for {M} cells")
+        return np.where(a < 0, a + M, a)
+
+    def block(self, rows, cols=None):
+        """cov[rows, cols] as an [a, b] ndarray: rows / cols are sequences of cell indices
+        (negative ones count from the end), slices, or None = all cells. One k_cov_block
+        launch; the M x M matrix is never formed."""
+        src = self._live()
+        return src.cov_block(self._cells(rows), self._cells(cols))
+
     def __getitem__(self, idx):
         if isinstance(idx, tuple) and len(idx) == 2 and all(isinstance(i, (int, np.integer)) for i in idx):
             i, j = (int(v) % self.var.shape[0] for v in idx)
-            if i == j:
+            if i == j and (self.source is None or all(-len(self) <= int(v) < len(self) for v in idx)):
                 return self.var[i]
+        if (self.source is not None and isinstance(idx, tuple) and len(idx) == 2
+                and all(isinstance(i, (int, np.integer, slice)) for i in idx)):
+            M = self.var.shape[0]
+            sel = []
+            for i in idx:
+                if isinstance(i, slice):
+                    sel.append(i)
+                else:
+                    if not -M <= int(i) < M:
+                        raise IndexError(f"index {int(i)} is out of bounds for axis of size {M}")
+                    sel.append([int(i)])
+            b = self.block(*sel)
+            # (an int drops its axis, as on an ndarray)
+            return b[tuple(slice(None) if isinstance(i, slice) else 0 for i in idx)]
         return self._dense()[idx]
 
     def _dense(self):
-        if self.var.shape[0] == 1:
+        if self.var.shape[0] == 1 and self.source is None:
             return self.var.reshape(1, 1).copy()
-        raise TypeError("DiagCov holds only the diagonal of the posterior covariance (the off-diagonal "
-                        "entries are never computed); use np.diag(cov) / np.amax(cov)")
+        src = self._live()
+        if self._cache is None:
+            M = self.var.shape[0]
+            if 8 * M * M > self.DENSE_MAX_BYTES:
+                raise MemoryError(f"the dense {M} x {M} covariance takes {8 * M * M} bytes, more than "
+                                  f"DiagCov.DENSE_MAX_BYTES = {self.DENSE_MAX_BYTES}; take the entries you need "
+                                  "with cov.block(rows, cols)")
+            d = src.cov_block(None, None)
+            d.flags.writeable = False   # (shared by every later use of this covariance)
+            self._cache = d
+        return self._cache
 
     def __array__(self, dtype=None, copy=None):
         d = self._dense()
-        return d if dtype is None else d.astype(dtype)
+        if dtype is not None and np.dtype(dtype) != d.dtype:
+            return d.astype(dtype)
+        return d.copy() if copy else d
 
     def __array_function__(self, func, types, args, kwargs):
         if func in (np.diag, np.diagonal):
@@ -176,8 +261,29 @@ class _DeviceGP:
         self._grid_to_device(X_star)
         # (the arrays are the model's pinned result buffer, handed over: no copy;
         # with the max / argmax of var its launch reduced, when it did)
-        mu, var, fused = self._dev().predict_view(with_max=True)
-        return mu.reshape(-1, 1), DiagCov(var, fused)
+        m = self._dev()
+        mu, var, fused = m.predict_view(with_max=True)
+        if m.dtype != _lib.F64:   # (an fp32 V serves no covariance blocks: the diagonal only)
+            return mu.reshape(-1, 1), DiagCov(var, fused)
+        return mu.reshape(-1, 1), DiagCov(var, fused, source=m, serial=m.serial())
+
+    def draw_prior_samples(self, X_star, N_samples=1):
+        """gaussian_process.py:180-191: N_samples joint draws of the zero-mean prior at
+        X_star -> [n, N_samples]. K is the prior covariance k**(X_star, X_star) computed
+        on the device (SF: s k; MF: the hifi prior rho^2 s_L k_L + s_H k_H); the draw is
+        numpy's (np.random.multivariate_normal, the global generator) as there."""
+        self._push_hyp()
+        self._grid_to_device(X_star)
+        K = self._dev().cov_block(None, None, prior=True)
+        return np.random.multivariate_normal(np.zeros(K.shape[0]), K, N_samples).T
+
+    def draw_posterior_samples(self, X_star, N_samples=1):
+        """gaussian_process.py:193-217: N_samples joint draws of the posterior at X_star ->
+        [n, N_samples]. These are draws of predict(X_star)'s posterior (mean with the
+        prior mean and centred observations, gp:132-143 / 414-432); the reference's
+        method leaves both out (gp:210-211), see DESIGN.md section 9."""
+        mu, cov = self.predict(X_star)
+        return np.random.multivariate_normal(mu.flatten(), np.asarray(cov), N_samples).T
 
     @property
     def L(self):
