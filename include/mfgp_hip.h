@@ -215,6 +215,37 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
  * whether the model still holds that posterior. No device work. */
 int mfgp_model_serial(const mfgp_model* m, uint64_t* serial);
 
+/* The posterior at arbitrary points, optionally conditioned on prospective points
+ * that are not in the model (MFGP.pred_var, gp:440-481; get_neg_var, gp:544-563):
+ * Xq [nq,2] query points (hifi targets, as in predict); XL_new [nl_new,2] /
+ * XH_new [nh_new,2] prospective lofi / hifi rows, at most MFGP_LOOK_MAX together
+ * (an SF model takes its rows in XH_new; nl_new must be 0). Prospective rows carry
+ * no values: they change the variance, not the mean. Outputs, each or NULL:
+ *   mu [nq]    posterior mean of the current model
+ *   var0 [nq]  posterior variance of the current model
+ *   var [nq]   variance with the prospective rows added (== var0 without any)
+ *   cov [nq, ldc] row-major, ldc >= nq: the dense look-ahead covariance
+ * Pointers are host or device memory. Every argument is checked before anything
+ * is enqueued (counts, ldc, finite coordinates: MFGP_ERR_ARG). The call settles a
+ * running launch and brings the factor up to date as mfgp_get_factor does (pending
+ * or deferred appends, new hyperparameters); it needs no grid. Of the model it
+ * changes nothing else but its look-ahead record and the two counters of
+ * mfgp_model_stats: rows, serial, grid, resident V and posterior, kept predict
+ * results and the path counters stay, so a predict before and after returns the
+ * same bits by the same path. The border of a prospective set (k_look_border) is
+ * kept in the record, keyed by the model's serial and the set's bytes and
+ * fidelities: a repeated call with the same set on an unchanged model runs
+ * k_look_query only. The record is allocated at the first call, freed with the
+ * model and not copied by mfgp_clone. A border that is not positive definite
+ * returns MFGP_ERR_NOT_PD (np.linalg.cholesky raising inside pred_var). A query's
+ * mu / var0 / var bits depend on its own point only, not on its place in Xq or on
+ * the other points. MFGP_F32 models are served in full fp64 (factor, Linv and z
+ * are fp64; V is not involved). */
+#define MFGP_LOOK_MAX 64   /* prospective points per call */
+int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq,
+               const double* XL_new, int64_t nl_new, const double* XH_new, int64_t nh_new,
+               double* mu, double* var0, double* var, double* cov, int64_t ldc);
+
 /* Sizes and state readers (the Python mirror's .X/.L attributes). */
 int64_t mfgp_model_n(const mfgp_model* m);      /* N = NL + NH */
 int64_t mfgp_model_nl(const mfgp_model* m);
@@ -229,7 +260,8 @@ int64_t mfgp_model_m(const mfgp_model* m);
  * second launch (k_lat_gemm2 or k_lat_gemm3), batch predicts served from the
  * resident posterior because the model appended nothing (k_post_copy), eager
  * appends of one GP that returned at the launch's published L22 verdict
- * (mfgp_append above)}; n <= 14. */
+ * (mfgp_append above), k_look_border launches and k_look_query launches of
+ * mfgp_query (index 14 look_border, 15 look_query)}; n <= 16. */
 int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n);
 /* Copy the lower Cholesky factor L [N,N] (row-major, zeros above the diagonal). */
 int mfgp_get_factor(mfgp_model* m, double* L_out);

@@ -5,6 +5,7 @@ is visible, every entry point raises instead of computing on the host.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import threading
@@ -16,6 +17,8 @@ LIB_PATH = os.environ.get("MFGP_LIB") or os.path.join(HERE, "libmfgp_hip.so")
 
 OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE, ERR_NO_V = 0, 1, 2, 3, 4
 COV_PRIOR = 1
+LOOK_MAX = 64   # prospective points per query (MFGP_LOOK_MAX)
+QueryResult = collections.namedtuple("QueryResult", ("mu", "var0", "var", "cov"))
 SF, MF = 0, 1
 F64, F32 = 0, 1
 ASYNC = 1
@@ -74,6 +77,9 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_int)]),
     "mfgp_cov_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "mfgp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "mfgp_model_serial": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "mfgp_release_view": (ctypes.c_int, [ctypes.c_void_p]),
     "mfgp_view_max": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_int64_p, ctypes.POINTER(ctypes.c_int)]),
@@ -401,6 +407,32 @@ class Model:
         check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(buf.ctypes.data), nb, flags))
         return buf
 
+    def query(self, Xq, XL_new=None, XH_new=None, mu=True, var0=False, var=True, cov=False, ldc=None):
+        """The posterior at arbitrary points Xq [n, 2], optionally with prospective lofi /
+        hifi points XL_new / XH_new (at most LOOK_MAX together; an SF model takes its in
+        XH_new) that are not in the model (mfgp_query): QueryResult(mu, var0, var, cov)
+        with None for what was not asked for -- mu and var0 [n] of the current model,
+        var [n] with the prospective points added, cov the dense [n, n] look-ahead
+        covariance (ldc: its leading dimension, default n). The model's rows, grid,
+        resident V and posterior stay as they are."""
+        def pts(a):
+            if a is None:
+                return np.empty((0, 2), dtype=np.float64)
+            return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, 2))
+        Xq, XL, XH = pts(Xq), pts(XL_new), pts(XH_new)
+        n = Xq.shape[0]
+        ldc = n if ldc is None else int(ldc)
+        o_mu = np.empty(n, dtype=np.float64) if mu else None
+        o_v0 = np.empty(n, dtype=np.float64) if var0 else None
+        o_v = np.empty(n, dtype=np.float64) if var else None
+        o_c = np.empty((n, max(ldc, 1)), dtype=np.float64) if cov else None
+
+        def op(a):   # (an empty output is still asked for: a non-null pointer)
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+        check(lib().mfgp_query(self.handle, op(Xq), n, op(XL), XL.shape[0], op(XH), XH.shape[0],
+                               op(o_mu), op(o_v0), op(o_v), op(o_c), ldc))
+        return QueryResult(o_mu, o_v0, o_v, None if o_c is None else o_c[:, :n])
+
     def serial(self):
         """The model's posterior serial (mfgp_model_serial): changes whenever its rows,
         hyperparameters, jitter or grid change, and never repeats."""
@@ -430,12 +462,13 @@ class Model:
         {lattice_g2}: the lattice steps whose GEMM and cells ran as a second launch
         (k_lat_gemm2); {post_copy}: batch predicts served from the resident posterior
         because the model appended nothing (k_post_copy); {early_pd}: eager appends that
-        returned at the launch's published L22 verdict (mfgp_append, one GP)."""
-        out = (ctypes.c_int64 * 14)()
-        check(lib().mfgp_model_stats(self.handle, out, 14))
+        returned at the launch's published L22 verdict (mfgp_append, one GP);
+        {look_border, look_query}: the k_look_border / k_look_query launches of query()."""
+        out = (ctypes.c_int64 * 16)()
+        check(lib().mfgp_model_stats(self.handle, out, 16))
         keys = ("factor_rows", "v_rows", "full_factor", "inc_factor", "full_predict", "vstream",
                 "lattice_nx", "lattice_ny", "lattice", "lattice_virtual", "lattice_arg", "lattice_g2",
-                "post_copy", "early_pd")
+                "post_copy", "early_pd", "look_border", "look_query")
         return dict(zip(keys, (int(v) for v in out)))
 
     def sample_points(self, threshold, max_points):

@@ -163,6 +163,19 @@ struct mfgp_ctx {
   int64_t plan_stats[PLAN_NSTATS] = {0};
 };
 
+// The look-ahead record of a model (mfgp_query): the border of its last prospective
+// set, keyed by the model's serial and the set's rows and fidelities.
+struct mfgp_look_rec {
+  double* W = nullptr;       // [wld][64]: L^-1 K(X, X_P)
+  int64_t wld = 0;
+  double* L22 = nullptr;     // [64][64] | L22inv [64][64] | ppts [64][2] (one allocation)
+  int* pfid = nullptr;       // [64] fidelities, then the border's status word
+  bool valid = false;        // the border below is stored for (serial, P, key)
+  uint64_t serial = 0;
+  int P = 0;
+  std::vector<double> key;   // the P rows (x, y), then their fidelities
+};
+
 struct mfgp_model {
   mfgp_ctx* ctx = nullptr;
   int* gate_dev = nullptr;  // device gate of every step of this model (the planners' loops: 0 = skip)
@@ -224,6 +237,8 @@ struct mfgp_model {
   int64_t n_lattice_g2 = 0;    // lattice steps whose GEMM and cells ran as a second launch (k_lat_gemm2)
   int64_t n_post_copy = 0;     // batch predicts served from the resident posterior (k_post_copy: nothing appended)
   int64_t n_early_pd = 0;      // eager appends that returned at the launch's published L22 verdict
+  mfgp_look_rec* look = nullptr;   // look-ahead record (allocated by the first mfgp_query, not cloned)
+  int64_t n_look_border = 0, n_look_query = 0;   // k_look_border / k_look_query launches
   unsigned* csr = nullptr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
   int64_t csr_n = 0;           // (bytes)
   // state generation: a new factor from scratch, a new grid or new hyperparameters
@@ -1656,6 +1671,12 @@ void mfgp_model_destroy(mfgp_model* m) {
   if (m->V) (void)hipFree(m->V);
   if (m->tred) (void)hipFree(m->tred);
   if (m->sync) (void)hipFree(m->sync);
+  if (m->look) {
+    if (m->look->W) (void)hipFree(m->look->W);
+    if (m->look->L22) (void)hipFree(m->look->L22);
+    if (m->look->pfid) (void)hipFree(m->look->pfid);
+    delete m->look;
+  }
   free_lat(m);
   delete m;
 }
@@ -2134,6 +2155,177 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
   return MFGP_OK;
 }
 
+// Look-ahead variance and off-grid queries (mfgp_look.hip). Queries run in chunks of
+// LOOK_CHUNK points (one k_look_query launch each) unless the covariance is wanted,
+// whose GEMM reads every tile of one scratch.
+constexpr int64_t LOOK_CHUNK = 16384;
+
+static bool all_finite(const double* p, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq, const double* XL_new, int64_t nl_new,
+               const double* XH_new, int64_t nh_new, double* mu, double* var0, double* var, double* cov,
+               int64_t ldc) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  mfgp_ctx* c = m->ctx;
+  if (nq < 0 || nl_new < 0 || nh_new < 0) return set_err(MFGP_ERR_ARG, "mfgp_query: negative count");
+  if (nl_new + nh_new > MFGP_LOOK_MAX)
+    return set_err(MFGP_ERR_ARG, "mfgp_query: at most %d prospective points per call (got %lld + %lld)", MFGP_LOOK_MAX,
+                   (long long)nl_new, (long long)nh_new);
+  if (m->kind == MFGP_SF && nl_new != 0)
+    return set_err(MFGP_ERR_ARG, "mfgp_query: a single-fidelity model takes its prospective rows in XH_new (nl_new = %lld)",
+                   (long long)nl_new);
+  if ((nq > 0 && !Xq) || (nl_new > 0 && !XL_new) || (nh_new > 0 && !XH_new))
+    return set_err(MFGP_ERR_ARG, "mfgp_query: null points");
+  if (cov && ldc < nq)
+    return set_err(MFGP_ERR_ARG, "mfgp_query: ldc = %lld is less than nq = %lld", (long long)ldc, (long long)nq);
+  const int P = (int)(nl_new + nh_new);
+  // host copies of the points: the finite check, the record's key, the upload
+  std::vector<double> hq((size_t)2 * nq), hp((size_t)2 * P);
+  auto fetch = [&](double* dst, const double* src, int64_t n) -> int {
+    if (n <= 0) return MFGP_OK;
+    if (is_device_ptr(src)) HIP_TRY(hipMemcpy(dst, src, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, sizeof(double) * 2 * n);
+    return MFGP_OK;
+  };
+  const bool q_dev = nq > 0 && is_device_ptr(Xq);
+  if ((rc = fetch(hq.data(), Xq, nq))) return rc;
+  if ((rc = fetch(hp.data(), XL_new, nl_new))) return rc;
+  if ((rc = fetch(hp.data() + 2 * nl_new, XH_new, nh_new))) return rc;
+  if (!all_finite(hq.data(), 2 * nq) || !all_finite(hp.data(), 2 * P))
+    return set_err(MFGP_ERR_ARG, "mfgp_query: the points must be finite");
+  if ((rc = update_factor(m))) return rc;
+  if (nq == 0 && P == 0) return MFGP_OK;
+  const int64_t N = m->NL + m->NH;
+  if (N > 0 && m->ld > MAX_FULL_CAP + 64)
+    return set_err(MFGP_ERR_ARG, "mfgp_query supports a training capacity of at most %lld rows (this model's is %lld)",
+                   (long long)MAX_FULL_CAP, (long long)(m->ld - 1));
+  LookArgs a{};
+  a.X = m->X;
+  a.A = m->A;
+  a.Linv = m->Linv;
+  a.zv = m->zv;
+  a.N = N;
+  a.NL = m->NL;
+  a.ld = m->ld;
+  a.h = derive_hyp(m->kind, m->hyp, m->jitter);
+  a.P = P;
+  if (P > 0) {
+    if (!m->look) m->look = new mfgp_look_rec();
+    mfgp_look_rec* k = m->look;
+    const int64_t wld = std::max<int64_t>(prow_blocks(N) * PRB, PRB);
+    if (!k->L22) {
+      HIP_TRY(hipMalloc(&k->L22, sizeof(double) * (2 * TILE + 2 * LOOK_MAX)));
+      HIP_TRY(hipMalloc(&k->pfid, sizeof(int) * (LOOK_MAX + 1)));
+    }
+    if (k->wld < wld) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (k->W) HIP_TRY(hipFree(k->W));
+      k->W = nullptr;
+      k->wld = 0;
+      k->valid = false;
+      HIP_TRY(hipMalloc(&k->W, sizeof(double) * wld * PBM));
+      k->wld = wld;
+    }
+    std::vector<double> key(hp);
+    for (int i = 0; i < P; ++i) key.push_back(i < nl_new ? 0.0 : 1.0);
+    a.W = k->W;
+    a.L22 = k->L22;
+    a.L22inv = k->L22 + TILE;
+    a.ppts = k->L22 + 2 * TILE;
+    a.pfid = k->pfid;
+    a.status = k->pfid + LOOK_MAX;
+    const bool hit = k->valid && k->serial == m->serial && k->P == P && k->key.size() == key.size() &&
+                     std::memcmp(k->key.data(), key.data(), sizeof(double) * key.size()) == 0;
+    if (!hit) {
+      int fid[LOOK_MAX];
+      for (int i = 0; i < P; ++i) fid[i] = i < nl_new ? 0 : 1;
+      k->valid = false;
+      HIP_TRY(hipMemcpyAsync(k->L22 + 2 * TILE, hp.data(), sizeof(double) * 2 * P, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(k->pfid, fid, sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
+      LookArgs b = a;
+      b.vld = k->wld;
+      HIP_TRY(launch_look_border(b, c->stream));
+      m->n_look_border += 1;
+      if ((rc = ensure_h_status(c, 1))) return rc;
+      HIP_TRY(hipMemcpyAsync(c->h_status, a.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));   // (also: hp / fid are read)
+      if (c->h_status[0] != INT_MAX)
+        return set_err(MFGP_ERR_NOT_PD, "Matrix is not positive definite (look-ahead border, prospective point %d)",
+                       c->h_status[0] - 1);
+      k->valid = true;
+      k->serial = m->serial;
+      k->P = P;
+      k->key.swap(key);
+    }
+  }
+  if (nq == 0) return MFGP_OK;
+  // workspace: [query points | mu | var0 | var (a chunk each) | cov when it goes to the host | scratch tiles]
+  const int64_t chunk = cov ? nq : std::min(nq, LOOK_CHUNK);
+  const int64_t vld = prow_blocks(N) * PRB + LOOK_MAX;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const bool cov_host = cov && !is_device_ptr(cov);
+  const size_t o_q = 0, o_out = o_q + up(sizeof(double) * 2 * chunk), o_cov = o_out + 3 * up(sizeof(double) * chunk);
+  const size_t o_scr = o_cov + (cov_host ? up(sizeof(double) * (size_t)nq * nq) : 0);
+  if ((rc = ensure_ws(c, o_scr + sizeof(double) * (size_t)ntiles_grid(chunk) * vld * PBM))) return rc;
+  char* ws = reinterpret_cast<char*>(c->ws);
+  double* outs[3] = {mu, var0, var};
+  a.scr = reinterpret_cast<double*>(ws + o_scr);
+  a.vld = vld;
+  a.store_t = cov ? 1 : 0;
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t n = std::min(chunk, nq - q0);
+    double* dq = reinterpret_cast<double*>(ws + o_q);
+    if (q_dev) {
+      dq = const_cast<double*>(Xq) + 2 * q0;
+    } else {
+      HIP_TRY(hipMemcpyAsync(dq, hq.data() + 2 * q0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    }
+    a.pts = dq;
+    a.M = n;
+    double* kout[3];
+    bool khost[3];
+    for (int i = 0; i < 3; ++i) {
+      khost[i] = outs[i] && !is_device_ptr(outs[i]);
+      kout[i] = !outs[i] ? nullptr
+                         : (khost[i] ? reinterpret_cast<double*>(ws + o_out + i * up(sizeof(double) * chunk))
+                                     : outs[i] + q0);
+    }
+    a.mu = kout[0];
+    a.var0 = kout[1];
+    a.var = kout[2];
+    HIP_TRY(launch_look_query(a, c->stream));
+    m->n_look_query += 1;
+    if (cov) {
+      // the scratch as a V of N + P rows over the query points: k_cov_block's GEMM
+      GPDesc d{};
+      d.V = a.scr;
+      d.vld = vld;
+      d.grid = dq;
+      d.M = n;
+      d.N = N + P;
+      d.hp = a.h;
+      double* kc = cov_host ? reinterpret_cast<double*>(ws + o_cov) : cov;
+      const int64_t kld = cov_host ? nq : ldc;
+      HIP_TRY(launch_cov_block(d, nullptr, n, nullptr, n, kc, kld, d.N == 0 ? 1 : 0, c->stream));
+      if (cov_host)
+        HIP_TRY(hipMemcpy2DAsync(cov, sizeof(double) * ldc, kc, sizeof(double) * nq, sizeof(double) * nq, nq,
+                                 hipMemcpyDeviceToHost, c->stream));
+    }
+    for (int i = 0; i < 3; ++i)
+      if (khost[i])
+        HIP_TRY(hipMemcpyAsync(outs[i] + q0, kout[i], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the chunk's staging is reused by the next
+  }
+  return MFGP_OK;
+}
+
 int mfgp_model_serial(const mfgp_model* m, uint64_t* serial) {
   if (!m || !serial) return set_err(MFGP_ERR_ARG, "null model/out");
   *serial = m->serial;
@@ -2156,10 +2348,11 @@ int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n) {
     if (m->kind == MFGP_MF) HIP_TRY(hipMemcpy(&nv[1], m->zvl + m->zb_rows + 1, sizeof(int), hipMemcpyDeviceToHost));
     virt = (int64_t)nv[0] + nv[1];
   }
-  const int64_t v[14] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
+  const int64_t v[16] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
                          m->n_full_predict, m->n_vstream, m->lat.nx, m->lat.ny, m->n_lattice, virt,
-                         m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd};
-  for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                         m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd,
+                         m->n_look_border, m->n_look_query};
+  for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   return MFGP_OK;
 }
 int64_t mfgp_model_nl(const mfgp_model* m) { return m ? m->NL : -1; }

@@ -261,6 +261,35 @@ hipError_t launch_post_copy(const PostCopy* h, int count, hipStream_t s);
 // na / nb = M); prior_only: the k** term alone. Descriptor by value.
 hipError_t launch_cov_block(const GPDesc& d, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
                             double* out, int64_t ldo, int prior_only, hipStream_t s);
+// look-ahead variance and off-grid queries (k_look_border, k_look_query; mfgp_look.hip).
+// The factor side is the model's (A, Linv, zv for its N rows, current for h); the
+// record side (W, L22, L22inv, ppts, pfid, status) is the model's look-ahead record.
+constexpr int LOOK_MAX = 64;   // prospective points per border (= MFGP_LOOK_MAX)
+struct LookArgs {
+  const double* X;       // [N,2] training rows: lofi [0,NL), hifi [NL,N)
+  const double* A;       // the factor, column-major [ld,ld]
+  const double* Linv;    // inverses of its diagonal blocks
+  const double* zv;      // [N] z = L^-1 (y - m)
+  int64_t N, NL, ld;
+  Hyp h;
+  const double* pts;     // k_look_query: the query points [M,2] (hifi targets)
+  int64_t M;
+  double* scr;           // k_look_query: scratch tiles [ceil(M/64)][vld][64]
+  int64_t vld;           // rows of a scratch tile (>= N + LOOK_MAX), of W for k_look_border (>= N)
+  double* W;             // [>= N][64]: W = L^-1 K(X, X_P), column p = prospective point p
+  double* L22;           // [64][64] column-major factor of the border's Schur complement
+  double* L22inv;        // its inverse, column-major (identity on rows / columns >= P)
+  const double* ppts;    // [P,2] prospective points
+  const int* pfid;       // [P] their fidelities: 0 = lofi, 1 = hifi
+  int* status;           // k_look_border: INT_MAX = ok, else 1 + the first non-positive pivot's row
+  int P;                 // prospective points (0: none, k_look_query skips the border block)
+  int store_t;           // k_look_query: 1 = also store t as rows N .. N + P - 1 of the scratch tile
+  double* mu;            // [M] outputs, each or null
+  double* var0;
+  double* var;
+};
+hipError_t launch_look_border(const LookArgs& a, hipStream_t s);
+hipError_t launch_look_query(const LookArgs& a, hipStream_t s);
 hipError_t launch_nlml_value(const GPDesc* d, int count, double* out, hipStream_t s);
 hipError_t launch_nlml_grad(const GPDesc* d, int64_t N, double* Xi, double* Kv, double* alpha, double* part,
                             hipStream_t s);

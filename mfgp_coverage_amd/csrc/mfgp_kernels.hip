@@ -21,13 +21,13 @@
 #include <climits>
 #include <cstring>
 #include "mfgp_internal.h"
-#include "mfgp_device.h"
-
-namespace mfgp {
 
 // Diagnostic phase stamps (tools/bench_diag.hip builds with -DMFGP_STAMPS); no-op otherwise.
+// Defined ahead of mfgp_device.h, whose factor_invert_64 stamps its phases.
 #ifdef MFGP_STAMPS
+namespace mfgp {
 __device__ long long* g_stamps;
+}
 #define STAMP(id)                                                                        \
   do {                                                                                   \
     if (threadIdx.x == 0 && blockIdx.x == 0) g_stamps[id] = __builtin_amdgcn_s_memtime(); \
@@ -37,6 +37,10 @@ __device__ long long* g_stamps;
   do {            \
   } while (0)
 #endif
+#include "mfgp_device.h"
+
+namespace mfgp {
+
 // k_inc_stream timeline stamps (GP 0 only; diagnostic builds)
 #ifdef MFGP_STAMPS
 #define FSTAMP(id)                                                                                 \
@@ -136,196 +140,7 @@ __global__ __launch_bounds__(NT) void k_assemble(const GPDesc* __restrict__ desc
 // on a real row is recorded in *status (LAPACK potrf's INFO, which NumPy turns
 // into LinAlgError, gp:254 / gp:529) and replaced by 1 to keep the batch finite.
 // ---------------------------------------------------------------------------
-constexpr int SP = NB + 1;   // padded row stride of the row-major LDS tiles
-constexpr int DB = 16;       // sub-block
-constexpr int DP = DB + 1;
-
-__device__ __forceinline__ double readlane_d(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
-// Broadcast lane k of each 16-lane DPP row to the whole row (row_newbcast:k, gfx90a+):
-// one v_mov_b64 with a 64-bit DPP source. The DPP control must be an immediate: the
-// switch folds away once the callers' fully unrolled loops make k a constant.
-// (s_nop 1: a DPP source written by the previous VALU instruction needs two wait
-// states, which the compiler does not count for inline assembly.)
-template <int K>
-__device__ __forceinline__ double bcast16_(double v) {
-  double r;
-  asm("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v), "i"(K));
-  return r;
-}
-// acc + (lane k's src) * mul (NEG: - ...), one v_fmac_f64 whose first source is the
-// row_newbcast:k DPP operand: a pivot chain's rank-1 update step, or a substitution
-// step, without a separate broadcast (fused multiply-add: the same rounding as
-// acc - b * mul written out)
-template <int K, bool NEG>
-__device__ __forceinline__ double fmac_bcast16_(double acc, double src, double mul) {
-  if (NEG)
-    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-                 : "+v"(acc) : "v"(src), "v"(mul), "i"(K));
-  else
-    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-                 : "+v"(acc) : "v"(src), "v"(mul), "i"(K));
-  return acc;
-}
-#define MFGP_BCAST16_CASES(F) \
-  F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14)
-__device__ __forceinline__ double bcast16(double v, int k) {
-  switch (k) {
-#define C_(K) case K: return bcast16_<K>(v);
-    MFGP_BCAST16_CASES(C_)
-#undef C_
-    default: return bcast16_<15>(v);
-  }
-}
-template <bool NEG>
-__device__ __forceinline__ double fmac_bcast16(double acc, double src, double mul, int k) {
-  switch (k) {
-#define C_(K) case K: return fmac_bcast16_<K, NEG>(acc, src, mul);
-    MFGP_BCAST16_CASES(C_)
-#undef C_
-    default: return fmac_bcast16_<15, NEG>(acc, src, mul);
-  }
-}
-
-// 16x16 f64 MFMA block product on LDS operands: acc (+/-)= A[16xK] * B[Kx16] with
-// A[i][k] = A[i*ars + k*acs], B[k][j] = B[k*brs + j*bcs].
-template <bool NEG>
-__device__ __forceinline__ d4 mfma16(const double* __restrict__ A, int ars, int acs, const double* __restrict__ B,
-                                     int brs, int bcs, int K, d4 acc, int lane) {
-  const int r = lane & 15, q = lane >> 4;
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    double a = A[r * ars + (k0 + q) * acs];
-    if (NEG) a = -a;
-    acc = mfma(a, B[(k0 + q) * brs + r * bcs], acc);
-  }
-  return acc;
-}
-
-// S: 64x64 row-major (stride SP), lower triangle = the matrix. On exit S = L
-// (zeros above the diagonal) and R = L^-1 (row-major, zeros above).
-__device__ void factor_invert_64(double* __restrict__ S, double* __restrict__ R,
-                                 double* __restrict__ U, int64_t g0, int64_t N, int* status) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r16 = lane & 15, q16 = lane >> 4;
-  for (int kk = 0; kk < NB / DB; ++kk) {
-    const int o = kk * DB;
-    if (w == 0) {
-      // (a) factor the 16x16 diagonal block in registers: lane r holds row o+(r&15)
-      //     (the four 16-lane DPP rows of the wave hold identical copies); column
-      //     values are broadcast inside each DPP row with row_newbcast, so no
-      //     SGPR/LDS round trip sits on the pivot chain. LAPACK dpotf2 order:
-      //     pivot = sqrt(a_jj), column scaled by 1/pivot.
-      double d[DB];
-#pragma unroll
-      for (int c = 0; c < DB; ++c) d[c] = S[(o + r16) * SP + o + c];
-      double rdiag = 1.0;
-      int fail = INT_MAX;
-#pragma unroll
-      for (int j = 0; j < DB; ++j) {
-        double p = bcast16(d[j], j);
-        const int64_t g = g0 + o + j;
-        const bool pad = g >= N;
-        const bool bad = !pad && !(p > 0.0);
-        fail = bad ? min(fail, (int)(g + 1)) : fail;
-        p = (pad || bad) ? 1.0 : p;
-        const double rs = rsqrt(p);
-        const double l = (r16 >= j) ? (r16 == j ? p : d[j]) * rs : 0.0;
-        rdiag = (r16 == j) ? rs : rdiag;
-        d[j] = l;
-        // d[k] -= l_r l_k for every row r: rows r > j are the update; rows r < j have
-        // l_r = 0; row j's columns k > j are above the diagonal (never read: the
-        // store below and the substitution read columns <= the row)
-#pragma unroll
-        for (int k = j + 1; k < DB; ++k) d[k] = fmac_bcast16<true>(d[k], l, l, k);
-      }
-      if (fail != INT_MAX && lane == 0) atomicMin(status, fail);
-      if (lane < DB) {
-#pragma unroll
-        for (int c = 0; c < DB; ++c) S[(o + lane) * SP + o + c] = (c <= lane) ? d[c] : 0.0;
-      }
-      // inverse of the 16x16 factor: lane c solves column c = r16 by forward
-      // substitution; L[i][m] is register m of DPP-row lane i.
-      double x[DB];
-#pragma unroll
-      for (int i = 0; i < DB; ++i) {
-        double s0 = (i == r16) ? 1.0 : 0.0, s1 = 0.0;
-#pragma unroll
-        for (int m = 0; m < i; ++m) {   // s -= L[i][m] x[m]
-          if (m & 1) s1 = fmac_bcast16<true>(s1, d[m], x[m], i);
-          else s0 = fmac_bcast16<true>(s0, d[m], x[m], i);
-        }
-        x[i] = (s0 + s1) * bcast16(rdiag, i);
-      }
-      // column c of Dinv (zero above the diagonal) into R's diagonal block
-      if (lane < DB) {
-#pragma unroll
-        for (int i = 0; i < DB; ++i) R[(o + i) * SP + o + lane] = x[i];
-      }
-    } else if (kk == 0) {
-      // the other waves meanwhile: R's blocks above the diagonal are zero
-      for (int e = tid - 64; e < 6 * DB * DB; e += NT - 64) {
-        const int b = e >> 8, i = (e >> 4) & 15, j = e & 15;   // blocks (0,1..3), (1,2..3), (2,3)
-        const int I = b < 3 ? 0 : (b < 5 ? 1 : 2), J = b < 3 ? b + 1 : (b < 5 ? b - 1 : 3);
-        R[(I * DB + i) * SP + J * DB + j] = 0.0;
-      }
-    }
-    __syncthreads();
-    STAMP(2 + 3 * kk);
-    const int nrest = NB / DB - 1 - kk;   // 16-row blocks below the diagonal block
-    // (b) sub-panel P = A_sub * Dinv^T, one 16x16 block per wave (MFMA)
-    if (w < nrest) {
-      const int R0 = o + DB + DB * w;
-      d4 acc = {0.0, 0.0, 0.0, 0.0};
-      acc = mfma16<false>(S + R0 * SP + o, SP, 1, R + o * SP + o, 1, SP, DB, acc, lane);   // B[k][j] = Dinv[j][k]
-#pragma unroll
-      for (int v = 0; v < 4; ++v) S[(R0 + q16 + 4 * v) * SP + o + r16] = acc[v];
-    }
-    __syncthreads();
-    STAMP(3 + 3 * kk);
-    // (c) trailing update of the lower 16x16 blocks of rows/cols [o+16, 64) (MFMA)
-    for (int t = w; t < nrest * (nrest + 1) / 2; t += NT / 64) {
-      int bi = 0;
-      while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
-      const int bj = t - bi * (bi + 1) / 2;
-      const int R0 = o + DB + DB * bi, C0 = o + DB + DB * bj;
-      d4 acc;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) acc[v] = S[(R0 + q16 + 4 * v) * SP + C0 + r16];
-      acc = mfma16<true>(S + R0 * SP + o, SP, 1, S + C0 * SP + o, 1, SP, DB, acc, lane);
-#pragma unroll
-      for (int v = 0; v < 4; ++v) S[(R0 + q16 + 4 * v) * SP + C0 + r16] = acc[v];
-    }
-    __syncthreads();
-    STAMP(4 + 3 * kk);
-  }
-  // Linv: the diagonal blocks are in R (and the blocks above them zero); block rows
-  // I = 1..3 by substitution:
-  //   Linv_IJ = -Dinv_I * sum_{m=J}^{I-1} L_Im Linv_mJ      (MFMA, wave w -> J = w)
-  STAMP(14);
-  for (int I = 1; I < NB / DB; ++I) {
-    if (w < I) {
-      const int J = w;
-      d4 acc = {0.0, 0.0, 0.0, 0.0};
-      acc = mfma16<false>(S + (I * DB) * SP + J * DB, SP, 1, R + (J * DB) * SP + J * DB, SP, 1, (I - J) * DB, acc,
-                          lane);
-      double* Uj = U + J * DB * DP;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) Uj[(q16 + 4 * v) * DP + r16] = acc[v];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      d4 acc2 = {0.0, 0.0, 0.0, 0.0};
-      acc2 = mfma16<true>(R + (I * DB) * SP + I * DB, SP, 1, Uj, DP, 1, DB, acc2, lane);   // Dinv_I
-#pragma unroll
-      for (int v = 0; v < 4; ++v) R[(I * DB + q16 + 4 * v) * SP + J * DB + r16] = acc2[v];
-    }
-    __syncthreads();
-    STAMP(14 + I);
-  }
-}
+// (SP, DB, the DPP broadcasts, mfma16 and factor_invert_64: mfgp_device.h)
 
 __global__ __launch_bounds__(NT) void k_potrf_diag(const GPDesc* __restrict__ descs, int kb) {
   const GPDesc& d = descs[blockIdx.x];
@@ -535,79 +350,7 @@ __global__ __launch_bounds__(NT) void k_syrk_blk(const GPDesc* __restrict__ desc
 // HBM N/256 times -- the 128-row blocks halve that traffic against 64-row ones;
 // the second workgroup on the CU hides each one's psi / diagonal phases.
 // ---------------------------------------------------------------------------
-constexpr int KS = 16;                   // K depth of one pipeline step
-constexpr int NSTAGE = 3;
-constexpr int STAGE = KS * PW + KS * PBM;   // doubles per stage: As [KS][128] + Bs [KS][64]
-constexpr int GLDS_PER_STEP = (KS + KS * PBM / 128) / (PNT / 64);   // per wave: 4 (L) + 2 (V)
-
-// Buffer-descriptor LDS-DMA (buffer_load_dwordx4 ... lds): the lane part of the
-// source offset is a VGPR fixed for the whole kernel, the row/step part an SGPR,
-// so one DMA costs an s_mov to M0 and the load -- no per-row address VALU.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const double* base, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes > 0x7fffffff ? 0x7fffffff : bytes), 0x00020000);
-}
-
-__device__ __forceinline__ void dma_buf(__amdgpu_buffer_rsrc_t rs, double* dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)dst, 16, voff, soff, 0, 0);
-}
-// the same with the sc1 cache policy (aux 16): served by L2, never by a possibly
-// stale line of this CU's L1 -- for bytes another workgroup stored in this launch
-__device__ __forceinline__ void dma_buf_sc1(__amdgpu_buffer_rsrc_t rs, double* dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)dst, 16, voff, soff, 0, 16);
-}
-
-
-// Main-loop accumulator: wave wm owns rows wm*32.. x all 64 cells.
-struct AccP {
-  d4 c[2][4];
-};
-// Diagonal-step accumulator: wave owns 16 rows of a 64-row half x 64 cells.
-struct AccH {
-  d4 c[4];
-};
-
-// acc += A[32 rows of this wave][KS] * B[KS][64]  (acc holds -psi + sum L V)
-__device__ __forceinline__ void main_mma(const double* __restrict__ As, const double* __restrict__ Bs, AccP& acc,
-                                         int wm, int lane) {
-  const int r = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int k0 = 0; k0 < KS; k0 += 4) {
-    const int k = k0 + q;
-    double a[2], b[4];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) a[mt] = As[swzp(k, wm * 32 + mt * 16 + r)];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) b[nt] = Bs[swz(k, nt * 16 + r)];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc.c[mt][nt] = mfma(a[mt], b[nt], acc.c[mt][nt]);
-  }
-}
-
-// A fragments of a column-major 64x64 block (A[i][k] = G[k*lda + i]) for the 16
-// rows p16.. of this wave, all 16 K steps: frag[t] = A[p16 + r][4t + q].
-__device__ __forceinline__ void load_afrag(double* frag, const double* __restrict__ G, int64_t lda, int p16,
-                                           int lane) {
-  const int r = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < 16; ++t) frag[t] = gp(G)[(int64_t)(4 * t + q) * lda + p16 + r];
-}
-
-// acc (+/-)= A[16 x 4*nt4] (fragments) * img[rows rb..][64 cells]; nt4 K steps
-template <bool NEG>
-__device__ __forceinline__ void half_mma(const double* frag, const double* __restrict__ img, int rb, AccH& acc,
-                                         int nt4, int lane) {
-  const int r = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < 16; ++t) {
-    if (t < nt4) {
-      const double a = NEG ? -frag[t] : frag[t];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc.c[nt] = mfma(a, img[swz(rb + 4 * t + q, nt * 16 + r)], acc.c[nt]);
-    }
-  }
-}
+// (the ring constants, the LDS-DMA forms, main_mma, load_afrag and half_mma: mfgp_device.h)
 
 // Fused np.amax / np.argmax of a GP's variance (simulator.py:672, 842, 1014 and
 // the argmax of compute_sample_points, sim:352). Every cell tile publishes its

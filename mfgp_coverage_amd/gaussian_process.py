@@ -28,9 +28,15 @@ Differences from the reference, all on the output side of the contract:
   gradient in place of autograd (``likelihood_and_grad``).
 * ``draw_prior_samples`` / ``draw_posterior_samples`` (gp:180-217) draw from the
   device's covariance; the posterior draws are of ``predict``'s posterior (the
-  reference's omit the prior mean and do not centre y). The other unused extras
-  (``ExpectedImprovement``, ``pred_var``, ``get_*_var``) are out of scope of
-  this engine.
+  reference's omit the prior mean and do not centre y).
+* ``predict_at`` (new), ``MFGP.pred_var`` / ``pred_var_diag`` / ``get_neg_var`` /
+  ``get_max_var`` (gp:440-481, 544-578) and ``SFGP.ExpectedImprovement``
+  (gp:150-178) evaluate the posterior at arbitrary points, with prospective points
+  that are not in the model, from the resident factor (k_look_border /
+  k_look_query): the grid, the resident V and the posterior stay as they are.
+  ``ExpectedImprovement`` uses ``predict``'s posterior (the reference's mean there
+  has no prior mean and uncentred y), and ``get_max_var``'s differential evolution
+  updates per generation, one launch each.
 """
 from __future__ import annotations
 
@@ -285,6 +291,20 @@ class _DeviceGP:
         mu, cov = self.predict(X_star)
         return np.random.multivariate_normal(mu.flatten(), np.asarray(cov), N_samples).T
 
+    def _query(self, X, X_L_new=None, X_H_new=None, **want):
+        """_lib.Model.query on the current data and hyperparameters (no grid involved)."""
+        self._sync_data()
+        self._push_hyp()
+        return self._dev().query(_as2(X), None if X_L_new is None else _as2(X_L_new),
+                                 None if X_H_new is None else _as2(X_H_new), **want)
+
+    def predict_at(self, X):
+        """(mu [n,1], var [n]): predict's posterior mean and variance at the arbitrary
+        points X [n,D], from the resident factor. Unlike predict(X) it leaves the grid,
+        the resident V and the resident posterior as they are."""
+        q = self._query(X, mu=True, var=True)
+        return q.mu.reshape(-1, 1), q.var
+
     @property
     def L(self):
         """Lower Cholesky factor of K + jitter*I (gp:254 / gp:529), downloaded on demand."""
@@ -398,6 +418,17 @@ class SFGP(_DeviceGP):
         """gaussian_process.py:121-148 -> (mu [M,1], DiagCov of the posterior covariance)."""
         return self._predict_dev(X_star)
 
+    def ExpectedImprovement(self, X_star):
+        """gaussian_process.py:150-178 -> [n,1]: gp:171-176 applied to predict's posterior
+        at X_star (predict_at; the reference's own mean there has no prior mean and
+        uncentred y)."""
+        from scipy.stats import norm
+        mu, var = self.predict_at(X_star)
+        v = np.abs(var).reshape(-1, 1)       # gp:171: |variance|, not its root
+        gain = np.min(self.y) - mu           # gp:174: the best observed value minus the mean
+        z = gain / v                         # gp:175
+        return gain * norm.cdf(z) + v * norm.pdf(z)   # gp:176
+
 
 class MFGP(_DeviceGP):
     """Two-level AR(1) multi-fidelity GP (gaussian_process.py:271-578) on the GPU."""
@@ -474,3 +505,50 @@ class MFGP(_DeviceGP):
         """gaussian_process.py:401-438 -> (mu [M,1], DiagCov of the posterior covariance)."""
         return self._predict_dev(X_star)
 
+    def pred_var(self, x, X_L_new, X_H_new):
+        """gaussian_process.py:440-481: the dense [n,n] posterior covariance at x with the
+        prospective points X_L_new / X_H_new (at most _lib.LOOK_MAX together) added to the
+        model, which stays as it is. MemoryError above DiagCov.DENSE_MAX_BYTES;
+        pred_var_diag gives the diagonal without the matrix."""
+        n = _as2(x).shape[0]
+        if 8 * n * n > DiagCov.DENSE_MAX_BYTES:
+            raise MemoryError(f"the dense {n} x {n} covariance takes {8 * n * n} bytes, more than "
+                              f"DiagCov.DENSE_MAX_BYTES = {DiagCov.DENSE_MAX_BYTES}; use pred_var_diag")
+        return self._query(x, X_L_new, X_H_new, mu=False, var=False, cov=True).cov
+
+    def pred_var_diag(self, x, X_L_new, X_H_new):
+        """np.diag(pred_var(x, X_L_new, X_H_new)) -> [n], without forming the matrix."""
+        return self._query(x, X_L_new, X_H_new, mu=False, var=True).var
+
+    def _neg_var_many(self, X, thrd, c, X_L_new, X_H_new):
+        """get_neg_var at every row of X [n,2] -> [n], one query launch."""
+        q = self._query(X, X_L_new, X_H_new, mu=True, var0=True, var=True)
+        return np.where(q.mu + c * q.var0 <= thrd, 0.0, -q.var)
+
+    def get_neg_var(self, x, thrd, c, X_L_new, X_H_new):
+        """gaussian_process.py:544-563: x is one point [D]; 0 where mean + c * var_old <= thrd
+        (the variance, not its root, as there), else minus the look-ahead variance at
+        x as a 1 x 1 array."""
+        x = np.asarray(x, dtype=np.float64)[None, :]
+        q = self._query(x, X_L_new, X_H_new, mu=True, var0=True, var=True)
+        if q.mu[0] + c * q.var0[0] <= thrd:
+            return 0
+        return -q.var.reshape(1, 1)
+
+    def get_max_var(self, Bounds, Thrd, c, X_L_new, X_H_new):
+        """gaussian_process.py:565-578 -> (x [1,D], value). scipy's differential evolution
+        as there (init='random'), but vectorised: a generation is one query launch
+        (updating='deferred'; the reference's updates point by point)."""
+        from scipy.optimize import differential_evolution
+        lo, hi = Bounds[0], Bounds[1]                 # gp:576 reads Bounds as [[x_lo, y_lo], [x_hi, y_hi]]
+        box = [(lo[0], hi[0]), (lo[1], hi[1])]
+
+        def neg_var(x, thrd, c_, xl, xh):
+            # a generation [D, S], or the polish step's single point [D]
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim == 1:
+                return self._neg_var_many(x[None, :], thrd, c_, xl, xh)[0]
+            return self._neg_var_many(x.T, thrd, c_, xl, xh)
+        res = differential_evolution(neg_var, box, args=(Thrd, c, X_L_new, X_H_new), init="random",
+                                     vectorized=True, updating="deferred")
+        return res.x.reshape(1, -1), -res.fun

@@ -119,11 +119,39 @@ def hand_off_report(path, names):
     return {k: poll_iterations(v) for k, v in dis.items() if any(n in k for n in names)}
 
 
-def kernel_report(path):
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def code_objects(path, workdir):
+    """The gfx950 code object of every translation unit: the library is linked without
+    -fgpu-rdc, so its .hip_fatbin section holds one offload bundle per unit, one after
+    the other (code_object above unbundles the first: mfgp_kernels.hip's)."""
+    fat = os.path.join(workdir, "fatbin_all.bin")
+    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", path, os.path.join(workdir, "y")],
+                   check=True, capture_output=True)
+    with open(fat, "rb") as fh:
+        blob = fh.read()
+    starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), blob)]
+    cos = []
+    for i, st in enumerate(starts):
+        part = os.path.join(workdir, f"bundle{i}.bin")
+        co = os.path.join(workdir, f"gfx950_{i}.co")
+        with open(part, "wb") as fh:
+            fh.write(blob[st:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}",
+                        f"--input={part}", f"--output={co}"], check=True, capture_output=True)
+        cos.append(co)
+    return cos
+
+
+def kernel_report(path, all_units=False):
+    """{kernel: resources} of the first translation unit's kernels (mfgp_kernels.hip), or
+    with all_units of every unit's."""
     with tempfile.TemporaryDirectory() as td:
-        co = code_object(path, td)
-        md = metadata(co)
-        cl = calls(co)
+        md, cl = [], {}
+        for co in (code_objects(path, td) if all_units else [code_object(path, td)]):
+            md += metadata(co)
+            cl.update(calls(co))
     rep = {}
     for k in md:
         name = k[".name"]
