@@ -323,8 +323,14 @@ int mfgp_batch_truncate(mfgp_model** models, int count, int64_t n_keep_hifi);
  * likelihood of the model's training data under the log-scaled hyperparameters
  * `hyp` (nhyp = 4 or 9; the model's own .hyp and factor are unchanged), and,
  * if grad != NULL, its gradient with respect to hyp ([nhyp]; the reference uses
- * autograd for it in train, gp:108-119 / 388-399). MFGP_ERR_NOT_PD as the
- * reference's cholesky raising LinAlgError. */
+ * autograd for it in train, gp:108-119 / 388-399). Unlike the data pointers of
+ * the other entry points, `hyp`, `nlml` and `grad` are HOST memory: hyp is read
+ * and *nlml / grad[] are written by the host. An empty model (N = 0) gives 0 and
+ * a zero gradient. The factor is of a scratch model with the model's jitter as it
+ * is set now (mfgp_model_set_hyp), on the model's context: a running launch of
+ * that context is waited for, a staged (deferred) append stays staged and its rows
+ * count. MFGP_ERR_NOT_PD as the reference's cholesky raising LinAlgError, and
+ * MFGP_ERR_ARG for nhyp other than the model's. */
 int mfgp_nlml(mfgp_model* m, const double* hyp, int nhyp, double* nlml, double* grad);
 
 /* Voronoi-cell reductions over the grid (simulator.py:194-323). Cell i is the

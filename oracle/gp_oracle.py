@@ -18,6 +18,10 @@ It restates, in NumPy, the single hot path of MSU-dcypherlab/mfgp-coverage
                           and a row-sum of squares (no M x M matrices). This is the
                           semantic spec of the HIP kernels and the stronger CPU
                           baseline.
+* ``nlml``             <- ``likelihood`` gp:81-106 / 344-385 with an analytic gradient;
+  ``nlml_extended``       the same formula wholly in 80-bit long double, the yardstick
+                          of both ``nlml`` and mfgp_nlml at tile edges
+                          (tests/golden/make_nlml_edges_golden.py).
 
 Pinning: ``tests/test_oracle.py`` checks this module
 against golden vectors produced by importing the reference itself in the build
@@ -365,3 +369,160 @@ def nlml(X, y, hyp, XL=None, yL=None, jitter=JITTER, grad=False):
         if dr[p] is not None:
             g[p] += a @ dr[p]
     return float(val), g
+
+
+# ---------------------------------------------------------------------------
+# The same NLML and gradient wholly in extended precision -- the yardstick of
+# nlml() above and of mfgp_nlml at block edges (tests/golden/
+# make_nlml_edges_golden.py). np.linalg does not take longdouble: the Cholesky
+# and the substitutions are plain row loops with vectorised inner products.
+# ---------------------------------------------------------------------------
+
+LD = np.longdouble
+
+
+def _require_extended():
+    eps = np.finfo(LD).eps
+    if not eps < 1e-18:
+        raise RuntimeError(f"np.longdouble has eps = {float(eps):.3g} here (not the 80-bit x87 format, eps 1.08e-19): "
+                           "nlml_extended would be no extended-precision reference on this platform")
+
+
+def _chol_ld(K):
+    """Lower Cholesky factor of a longdouble matrix, column by column."""
+    N = K.shape[0]
+    L = np.zeros((N, N), dtype=LD)
+    for j in range(N):
+        d = K[j, j] - L[j, :j] @ L[j, :j]
+        if not d > 0:
+            raise np.linalg.LinAlgError("Matrix is not positive definite")
+        L[j, j] = np.sqrt(d)
+        if j + 1 < N:
+            L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def _fwd_ld(L, B):
+    """L^-1 B by forward substitution (B [N] or [N, k])."""
+    Y = np.zeros_like(B)
+    for i in range(L.shape[0]):
+        Y[i] = (B[i] - L[i, :i] @ Y[:i]) / L[i, i]
+    return Y
+
+
+def _back_ld(L, B):
+    """L^-T B by back substitution."""
+    Y = np.zeros_like(B)
+    for i in range(L.shape[0] - 1, -1, -1):
+        Y[i] = (B[i] - L[i + 1:, i] @ Y[i + 1:]) / L[i, i]
+    return Y
+
+
+# exp and log from +, -, *, / alone. libm's expl / logl run the x87 f2xm1 / fyl2x
+# instructions, whose last bits differ from one CPU vendor to the next; cond(K)
+# amplifies that difference (measured between two hosts: 18 float64 ulp on the value
+# at cond 2.6e3, 3e-13 relative at cond 1.7e8). The basic operations are correctly
+# rounded everywhere, so these give the same bits on every x86-64 host.
+_LN2_HI = LD(6.93147180369123816490e-01)     # the leading 32 bits of ln 2: k * _LN2_HI is exact
+_LN2_LO = LD(1.90821492927058770002e-10)     # ln 2 - _LN2_HI
+_LN2 = _LN2_HI + _LN2_LO
+_PI = LD(3.141592653589793) + LD(1.2246467991473532e-16)      # pi = hi + lo (float64 each)
+
+
+def _exp_ld(x):
+    """exp(x) = 2^k exp(r), |r| <= ln(2) / 2, exp(r) by its Taylor series (Horner; the
+    22nd term is below 1e-31; r in two steps, the first exact). Relative error a few
+    eps (1.08e-19)."""
+    x = np.asarray(x, dtype=LD)
+    k = np.rint(x / _LN2)
+    r = (x - k * _LN2_HI) - k * _LN2_LO
+    s = np.ones_like(r)
+    for n in range(22, 0, -1):
+        s = LD(1) + r * s / LD(n)
+    return np.ldexp(s, k.astype(np.int64))
+
+
+def _log_ld(x):
+    """log(x), x > 0, by Newton's iteration y += x exp(-y) - 1 from e ln 2 + (m - 1)
+    (x = m 2^e; the first error is below 0.2 and squares in every step)."""
+    x = np.asarray(x, dtype=LD)
+    m, e = np.frexp(x)
+    y = e.astype(LD) * _LN2 + (m - LD(1))
+    for _ in range(7):
+        y = y + (x * _exp_ld(-y) - LD(1))
+    return y
+
+
+def _sq_dist_scaled_ld(x, log_l):
+    lx = _exp_ld(log_l)
+    d = x[:, None, :] / lx - x[None, :, :] / lx
+    return np.sum(d * d, axis=2)
+
+
+def nlml_extended(X, y, hyp, XL=None, yL=None, jitter=JITTER):
+    """nlml(..., grad=True) evaluated wholly in np.longdouble (80-bit on x86-64): kernel
+    assembly, exp and log (from the basic operations: _exp_ld, _log_ld), Cholesky, both
+    triangular solves, K^-1, the trace and the mean terms. The float64 inputs are taken as exact. Returns (value, grad) as longdouble.
+    Raises RuntimeError where longdouble is no wider than 64 bits of mantissa."""
+    _require_extended()
+    hyp = np.asarray(hyp, dtype=np.float64).astype(LD)
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 2).astype(LD)
+    y = np.asarray(y, dtype=np.float64).reshape(-1).astype(LD)
+    jit = LD(jitter)
+    one, half, two = LD(1), LD(0.5), LD(2)
+    if hyp.shape[0] == 4:
+        m, s, sn = _exp_ld(hyp[0]), _exp_ld(hyp[1]), _exp_ld(hyp[3])
+        N = X.shape[0]
+        r2 = _sq_dist_scaled_ld(X, hyp[2])
+        E = s * _exp_ld(-half * r2)
+        eye = np.eye(N, dtype=LD)
+        K = E + eye * sn + eye * jit
+        res = y - m
+        dK = [None, E, E * r2, eye * sn]
+        dr = [-m * np.ones(N, dtype=LD), None, None, None]
+    else:
+        XL = np.asarray(XL, dtype=np.float64).reshape(-1, 2).astype(LD)
+        yL = np.asarray(yL, dtype=np.float64).reshape(-1).astype(LD)
+        mL, sL, sH = _exp_ld(hyp[0]), _exp_ld(hyp[1]), _exp_ld(hyp[4])
+        rho, snL, snH = _exp_ld(hyp[6]), _exp_ld(hyp[7]), _exp_ld(hyp[8])
+        eH = _exp_ld(hyp[3])
+        mH = rho * mL + eH
+        NL, NH = XL.shape[0], X.shape[0]
+        N = NL + NH
+        Xa = np.vstack([XL, X])
+        rL2 = _sq_dist_scaled_ld(Xa, hyp[2])
+        rH2 = _sq_dist_scaled_ld(Xa, hyp[5])
+        EL = sL * _exp_ld(-half * rL2)
+        EH = sH * _exp_ld(-half * rH2)
+        lo = np.zeros(N, dtype=bool)
+        lo[:NL] = True
+        hi = ~lo
+        ll, hh = lo[:, None] & lo[None, :], hi[:, None] & hi[None, :]
+        zero = LD(0)
+        cL = np.where(ll, one, np.where(hh, rho * rho, rho)).astype(LD)
+        cH = np.where(hh, one, zero).astype(LD)
+        K = cL * EL + cH * EH + np.diag(np.where(lo, snL, snH)) + np.eye(N, dtype=LD) * jit
+        res = np.concatenate([yL - mL, y - mH])
+        drho = np.where(ll, zero, np.where(hh, two * rho * rho, rho)).astype(LD)
+        oL, oH = np.ones(NL, dtype=LD), np.ones(NH, dtype=LD)
+        dK = [None, cL * EL, cL * EL * rL2, None, cH * EH, cH * EH * rH2, drho * EL,
+              np.diag(np.where(lo, snL, zero)), np.diag(np.where(hi, snH, zero))]
+        dr = [np.concatenate([-mL * oL, -rho * mL * oH]), None, None,
+              np.concatenate([zero * oL, -eH * oH]), None, None,
+              np.concatenate([zero * oL, -rho * mL * oH]), None, None]
+    g = np.zeros(hyp.shape[0], dtype=LD)
+    if N == 0:
+        return LD(0), g
+    assert K.dtype == LD and res.dtype == LD
+    L = _chol_ld(K)
+    a = _back_ld(L, _fwd_ld(L, res))
+    val = half * (res @ a) + np.sum(_log_ld(np.diag(L))) + half * _log_ld(two * _PI) * LD(N)
+    Kinv = _back_ld(L, _fwd_ld(L, np.eye(N, dtype=LD)))
+    W = Kinv - np.outer(a, a)
+    for p in range(hyp.shape[0]):
+        if dK[p] is not None:
+            g[p] += half * np.sum(W * dK[p])
+        if dr[p] is not None:
+            g[p] += a @ dr[p]
+    assert val.dtype == LD and g.dtype == LD
+    return val, g

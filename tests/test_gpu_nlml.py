@@ -40,7 +40,16 @@ def test_nlml_vs_reference(nl, c):
     _, go = O.nlml(X, y, h, grad=True, **kw)
     fd = nl[c + "_fdgrad"]
     well = c.endswith("h1")      # h0: the trained noise (e^-37.8 SF) leaves K nearly singular
-    assert np.all(np.abs(g - go) <= (1e-8 if well else 1e-3) * np.maximum(np.abs(go), 1.0)), (g, go)
+    # h0 against the oracle: device and fp64 oracle each within 16 eps cond(K) max(N, 64) of the
+    # truth (the bound of tests/_nlml_edges.py; cond 7e7 .. 3.5e8 here: 3e-5 .. 2.4e-4). The
+    # oracle is within 1.6e-9 of the extended-precision gradient on these cases; the finite
+    # differences themselves are off by up to 4e-4, hence the 1e-3 against them.
+    if well:
+        tol_o = 1e-8
+    else:
+        K = O.mf_K(kw["XL"], X, h) if kw else O.se_kernel(X, X, h[1], h[2]) + np.eye(n) * (np.exp(h[-1]) + O.JITTER)
+        tol_o = min(1e-3, 32 * 2.22e-16 * np.linalg.cond(K, 2) * max(K.shape[0], 64))
+    assert np.all(np.abs(g - go) <= tol_o * np.maximum(np.abs(go), 1.0)), (g, go, tol_o)
     assert np.all(np.abs(g - fd) <= (1e-5 if well else 1e-3) * np.maximum(np.abs(fd), 1.0)), (g, fd)
 
 
