@@ -55,6 +55,10 @@ void mfgp_ctx_destroy(mfgp_ctx* ctx);
  * up to 16 GB, and the workspace) after synchronising; the next call that needs
  * it allocates it again. Models keep their resident state. */
 int mfgp_ctx_trim(mfgp_ctx* ctx);
+/* Members per set of launches for mfgp_nlml_batch: 0 = automatic (default: as many as
+ * 4 GiB of scratch hold, at most 256); a larger value is taken as 256. The results do
+ * not depend on it. Its scratch is given back by mfgp_ctx_trim as well. */
+int mfgp_ctx_set_nlml_chunk(mfgp_ctx* ctx, int max_members);
 /* Launch on a caller stream (hipStream_t) instead of the context's own. NULL restores it. */
 int mfgp_ctx_set_stream(mfgp_ctx* ctx, void* hip_stream);
 void* mfgp_ctx_get_stream(mfgp_ctx* ctx);
@@ -332,6 +336,31 @@ int mfgp_batch_truncate(mfgp_model** models, int count, int64_t n_keep_hifi);
  * count. MFGP_ERR_NOT_PD as the reference's cholesky raising LinAlgError, and
  * MFGP_ERR_ARG for nhyp other than the model's. */
 int mfgp_nlml(mfgp_model* m, const double* hyp, int nhyp, double* nlml, double* grad);
+
+/* likelihood / its gradient (mfgp_nlml) for S hyperparameter vectors over the model's
+ * data, in one set of launches per chunk of members (multi-start training, likelihood
+ * surfaces). hyps [S][nhyp], nlml [S], grad [S][nhyp] or NULL, status [S] or NULL:
+ * all HOST memory, as for mfgp_nlml, and the same preconditions: a running launch of
+ * the context is waited for, the model's jitter as it is set now, a staged (deferred)
+ * append stays staged and its rows count, an MFGP_F32 model is served in fp64, and
+ * the model keeps its rows, serial, factor, resident V / posterior, kept predict
+ * results and path counters.
+ * Bit equality: member s's value and gradient are, bit for bit, what
+ * mfgp_nlml(m, hyps + s * nhyp, nhyp, ..) returns. A member's bits therefore depend
+ * on its own vector only: not on S, on its position, on the other members, on the
+ * chunking (mfgp_ctx_set_nlml_chunk) or on whether grad was asked for.
+ * status[s] = 0: success; > 0: the order of the leading minor of K(hyps[s]) that is
+ * not positive definite (the number in mfgp_nlml's message); that member's nlml[s]
+ * and gradient are NaN and the other members are served as usual. With status ==
+ * NULL any such member makes the call return MFGP_ERR_NOT_PD, the outputs then
+ * unspecified. A device error fails the whole call. S == 0: MFGP_OK, nothing
+ * written. N = 0: value 0, a zero gradient and status 0 for every member.
+ * MFGP_ERR_ARG for nhyp other than the model's (mfgp_nlml's message), S < 0, or NULL
+ * hyps / nlml with S > 0. The members' scratch (factor storage, and L^-1 and K^-1 with
+ * the gradient) lives with the context: grown on demand, reused by the next call,
+ * given back by mfgp_ctx_trim / mfgp_ctx_destroy. */
+int mfgp_nlml_batch(mfgp_model* m, const double* hyps, int S, int nhyp,
+                    double* nlml, double* grad, int* status);
 
 /* Voronoi-cell reductions over the grid (simulator.py:194-323). Cell i is the
  * closed polygon verts[vstart[i] .. vstart[i+1]) ([.,2], vertices of the

@@ -31,6 +31,7 @@ SIGNATURES = {
     "mfgp_ctx_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "mfgp_ctx_destroy": (None, [ctypes.c_void_p]),
     "mfgp_ctx_trim": (ctypes.c_int, [ctypes.c_void_p]),
+    "mfgp_ctx_set_nlml_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mfgp_ctx_set_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mfgp_ctx_get_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "mfgp_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -45,6 +46,8 @@ SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "mfgp_model_stats": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, ctypes.c_int]),
     "mfgp_nlml": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, _c_double_p, ctypes.c_void_p]),
+    "mfgp_nlml_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
     "mfgp_cell_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -172,6 +175,11 @@ class Context:
         """Free the context's scratch (the MFGP_F32 full predict's fp64 V scratch and
         the workspace); models keep their state."""
         check(lib().mfgp_ctx_trim(self.handle))
+
+    def set_nlml_chunk(self, n):
+        """Members per set of launches of Model.nlml_batch (0: automatic, as many as its
+        scratch budget holds). The results do not depend on it."""
+        check(lib().mfgp_ctx_set_nlml_chunk(self.handle, int(n)))
 
     def set_stream(self, stream_ptr):
         check(lib().mfgp_ctx_set_stream(self.handle, ctypes.c_void_p(stream_ptr)))
@@ -487,6 +495,27 @@ class Model:
         check(lib().mfgp_nlml(self.handle, ptr(h), int(h.shape[0]), ctypes.byref(v),
                               ctypes.c_void_p(g.ctypes.data) if grad else None))
         return (v.value, g) if grad else v.value
+
+    def nlml_batch(self, hyps, grad=False, status=False):
+        """nlml for the S rows of hyps [S, nhyp] in one set of launches per chunk
+        (mfgp_nlml_batch): values [S], then grads [S, nhyp] if grad, then status [S] (int)
+        if status. Row s has the bits of nlml(hyps[s], grad). With status, a row that is
+        not positive definite gets status > 0 (the order of the failing leading minor) and
+        NaN outputs; without it, such a row raises LinAlgError."""
+        h = np.ascontiguousarray(hyps, dtype=np.float64)
+        if h.ndim != 2:
+            raise ValueError("hyps must be [S, nhyp]")
+        S, nhyp = h.shape
+        v = np.empty(S, dtype=np.float64)
+        g = np.empty((S, nhyp), dtype=np.float64) if grad else None
+        st = np.zeros(S, dtype=np.intc) if status else None
+        # (ptr() gives None for an empty array: pass the addresses themselves)
+        check(lib().mfgp_nlml_batch(self.handle, ctypes.c_void_p(h.ctypes.data), int(S), int(nhyp),
+                                    ctypes.c_void_p(v.ctypes.data),
+                                    ctypes.c_void_p(g.ctypes.data) if grad else None,
+                                    ctypes.c_void_p(st.ctypes.data) if status else None))
+        out = (v,) + ((g,) if grad else ()) + ((st.astype(np.int64),) if status else ())
+        return out if len(out) > 1 else v
 
     def truncate(self, n_keep_hifi):
         check(lib().mfgp_truncate(self.handle, int(n_keep_hifi)))

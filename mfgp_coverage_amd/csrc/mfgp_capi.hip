@@ -68,6 +68,9 @@ constexpr int RING = 64;       // descriptor upload slots
 constexpr int MAXB = 256;      // GPs per launch
 constexpr int64_t MAX_FULL_CAP = 16319;   // largest training capacity the full predict serves (ld <= 16383)
 constexpr size_t F32_SCRATCH = size_t(16) << 30;   // bytes of fp64 V scratch for MFGP_F32 full predicts
+// bytes of scratch a chunk of mfgp_nlml_batch may hold (a member: its factor A, and Xi
+// and Kv with the gradient, ld^2 doubles each): 40 members with the gradient at N = 2048
+constexpr size_t NLML_BATCH_SCRATCH = size_t(4) << 30;
 // lattice-separable step (k_inc_lat): taken when kss / (smallest noise + jitter)
 // <= LAT_RMAX (its error grows with the conditioning of K),
 // and for at most LAT_MAXD consecutive steps before var / mu are recomputed from V
@@ -155,6 +158,14 @@ struct mfgp_ctx {
   // pinned host staging of the status words
   int* h_status = nullptr;
   size_t h_status_n = 0;
+  // mfgp_nlml_batch: members per set of launches (0: as many as NLML_BATCH_SCRATCH
+  // holds) and its scratch (NlmlLayout), grown on demand, kept for the next call and
+  // given back by mfgp_ctx_trim
+  int nlml_chunk = 0;
+  double* nb_dev = nullptr;
+  size_t nb_dev_bytes = 0;
+  double* nb_host = nullptr;   // pinned
+  size_t nb_host_bytes = 0;
 
   int ncu = 256;              // compute units (hipDeviceProp multiProcessorCount)
   // the path counters of the planners' loops (mfgp_sample_points,
@@ -1377,6 +1388,107 @@ int copy_rows(mfgp_model* m, int64_t at, const double* X, const double* y, int64
   return MFGP_OK;
 }
 
+// The host finish of mfgp_nlml and of every member of mfgp_nlml_batch (one copy, so
+// that a member's bits are the single call's): the value from v = (sum log L_ii,
+// |z|^2), the gradient from the np tile partials hp (summed in tile order) and the
+// mean terms a^T dr/dh from ha = K^-1 r (summed in row order).
+void nlml_finish(const mfgp_model* m, const double* hyp, int64_t N, const double* v, const double* hp, int64_t np,
+                 const double* ha, double* nlml, double* grad) {
+  const int nhyp = m->nhyp;
+  // NLML = 1/2 r^T K^-1 r + sum log L_ii + N/2 log(2 pi)   (gp:104-105 / gp:383-384)
+  *nlml = 0.5 * v[1] + v[0] + 0.5 * std::log(2.0 * M_PI) * (double)N;
+  if (grad) {
+    for (int p = 0; p < nhyp; ++p) grad[p] = 0.0;
+    const int64_t ntiles = np / 9;
+    double g9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t tt = 0; tt < ntiles; ++tt)
+      for (int p = 0; p < 9; ++p) g9[p] += hp[tt * 9 + p];
+    // mean terms a^T dr/dh (r = y - m(hyp), gp:89-90 / gp:415-424)
+    const Hyp h = derive_hyp(m->kind, hyp, m->jitter);
+    double sa_lo = 0.0, sa_hi = 0.0;
+    for (int64_t i = 0; i < N; ++i) (i < m->NL ? sa_lo : sa_hi) += ha[i];
+    if (m->kind == MFGP_SF) {
+      grad[0] = -h.meanL * (sa_lo + sa_hi);
+      grad[1] = g9[1];
+      grad[2] = g9[2];
+      grad[3] = g9[3];
+    } else {
+      for (int p = 0; p < 9; ++p) grad[p] = g9[p];
+      grad[0] += -h.meanL * sa_lo - h.rho * h.meanL * sa_hi;
+      grad[3] += -std::exp(hyp[3]) * sa_hi;
+      grad[6] += -h.rho * h.meanL * sa_hi;
+    }
+  }
+}
+
+// ---- mfgp_nlml_batch: the context's scratch for a chunk of C members of leading
+// dimension ld (doubles, member-major inside each array):
+//   A [C][ld^2] | Linv [C][ld/64][TILE] | zv [C][ld] | val [C][2] | status [C] (ints)
+//   and with the gradient  Xi [C][ld^2] | Kv [C][ld^2] | alpha [C][ld] | part [C][np]
+// The pinned host image holds val | part | alpha of a chunk.
+struct NlmlLayout {
+  int64_t ld, np, C;
+  bool grad;
+  int64_t o_A, o_Li, o_zv, o_val, o_st, o_Xi, o_Kv, o_al, o_part, total;   // device offsets (doubles)
+  int64_t h_val, h_part, h_al, h_total;                                    // host offsets (doubles)
+};
+int64_t nlml_member_bytes(int64_t ld, int64_t np, bool grad) {
+  int64_t n = ld * ld + (ld / NB) * TILE + ld + 2 + 1;
+  if (grad) n += 2 * ld * ld + ld + np;
+  return n * (int64_t)sizeof(double);
+}
+NlmlLayout nlml_layout(int64_t ld, int64_t np, int64_t C, bool grad) {
+  NlmlLayout l{};
+  l.ld = ld;
+  l.np = np;
+  l.C = C;
+  l.grad = grad;
+  l.o_A = 0;
+  l.o_Li = l.o_A + C * ld * ld;
+  l.o_zv = l.o_Li + C * (ld / NB) * TILE;
+  l.o_val = l.o_zv + C * ld;
+  l.o_st = l.o_val + 2 * C;
+  l.o_Xi = round_up(l.o_st + (C + 1) / 2, NB);   // (the tile loads of Xi / Kv are 16-byte ones)
+  l.o_Kv = l.o_Xi + (grad ? C * ld * ld : 0);
+  l.o_al = l.o_Kv + (grad ? C * ld * ld : 0);
+  l.o_part = l.o_al + (grad ? C * ld : 0);
+  l.total = l.o_part + (grad ? C * np : 0);
+  l.h_val = 0;
+  l.h_part = 2 * C;
+  l.h_al = l.h_part + (grad ? C * np : 0);
+  l.h_total = l.h_al + (grad ? C * ld : 0);
+  return l;
+}
+int ensure_nlml_scratch(mfgp_ctx* c, const NlmlLayout& l) {
+  const size_t dev = sizeof(double) * (size_t)l.total, host = sizeof(double) * (size_t)l.h_total;
+  if (dev > c->nb_dev_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->nb_dev) HIP_TRY(hipFree(c->nb_dev));
+    c->nb_dev = nullptr;
+    c->nb_dev_bytes = 0;
+    HIP_TRY(hipMalloc(&c->nb_dev, dev));
+    c->nb_dev_bytes = dev;
+  }
+  if (host > c->nb_host_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->nb_host) HIP_TRY(hipHostFree(c->nb_host));
+    c->nb_host = nullptr;
+    c->nb_host_bytes = 0;
+    HIP_TRY(hipHostMalloc(&c->nb_host, host, hipHostMallocDefault));
+    c->nb_host_bytes = host;
+  }
+  return MFGP_OK;
+}
+int free_nlml_scratch(mfgp_ctx* c) {
+  if (c->nb_dev) HIP_TRY(hipFree(c->nb_dev));
+  c->nb_dev = nullptr;
+  c->nb_dev_bytes = 0;
+  if (c->nb_host) HIP_TRY(hipHostFree(c->nb_host));
+  c->nb_host = nullptr;
+  c->nb_host_bytes = 0;
+  return MFGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1448,6 +1560,7 @@ void mfgp_ctx_destroy(mfgp_ctx* c) {
   for (int i = 0; i < RING; ++i) (void)hipEventDestroy(c->ring_ev[i]);
   if (c->ws) (void)hipFree(c->ws);
   if (c->vscr) (void)hipFree(c->vscr);
+  (void)free_nlml_scratch(c);
   if (c->d_ring) (void)hipFree(c->d_ring);
   if (c->h_status) (void)hipHostFree(c->h_status);
   if (c->h_ring) (void)hipHostFree(c->h_ring);
@@ -1466,6 +1579,13 @@ int mfgp_ctx_trim(mfgp_ctx* c) {
   if (c->ws) HIP_TRY(hipFree(c->ws));
   c->ws = nullptr;
   c->ws_bytes = 0;
+  return free_nlml_scratch(c);
+}
+
+int mfgp_ctx_set_nlml_chunk(mfgp_ctx* c, int max_members) {
+  if (!c) return set_err(MFGP_ERR_ARG, "null ctx");
+  if (max_members < 0) return set_err(MFGP_ERR_ARG, "max_members must be >= 0 (0: automatic)");
+  c->nlml_chunk = std::min(max_members, MAXB);
   return MFGP_OK;
 }
 
@@ -3374,31 +3494,112 @@ int mfgp_nlml(mfgp_model* m, const double* hyp, int nhyp, double* nlml, double* 
     HIP_TRY(hipMemcpyAsync(ha.data(), al, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // NLML = 1/2 r^T K^-1 r + sum log L_ii + N/2 log(2 pi)   (gp:104-105 / gp:383-384)
-  *nlml = 0.5 * v[1] + v[0] + 0.5 * std::log(2.0 * M_PI) * (double)N;
-  if (grad) {
-    for (int p = 0; p < nhyp; ++p) grad[p] = 0.0;
-    const int64_t ntiles = np / 9;
-    double g9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t tt = 0; tt < ntiles; ++tt)
-      for (int p = 0; p < 9; ++p) g9[p] += hp[tt * 9 + p];
-    // mean terms a^T dr/dh (r = y - m(hyp), gp:89-90 / gp:415-424)
-    const Hyp h = derive_hyp(m->kind, hyp, m->jitter);
-    double sa_lo = 0.0, sa_hi = 0.0;
-    for (int64_t i = 0; i < N; ++i) (i < m->NL ? sa_lo : sa_hi) += ha[i];
-    if (m->kind == MFGP_SF) {
-      grad[0] = -h.meanL * (sa_lo + sa_hi);
-      grad[1] = g9[1];
-      grad[2] = g9[2];
-      grad[3] = g9[3];
-    } else {
-      for (int p = 0; p < 9; ++p) grad[p] = g9[p];
-      grad[0] += -h.meanL * sa_lo - h.rho * h.meanL * sa_hi;
-      grad[3] += -std::exp(hyp[3]) * sa_hi;
-      grad[6] += -h.rho * h.meanL * sa_hi;
+  nlml_finish(m, hyp, N, v, hp.data(), np, ha.data(), nlml, grad);
+  return done(MFGP_OK);
+}
+
+// mfgp_nlml for S hyperparameter vectors in chunks of C members: per chunk one
+// batched factor (enqueue_factor), one read of the members' status words, one launch
+// each of k_nlml_value and the four gradient kernels, one synchronisation. The
+// members are scratch factors in the context's scratch that read the caller's X / y
+// in place; the caller's model is not written.
+int mfgp_nlml_batch(mfgp_model* m, const double* hyps, int S, int nhyp, double* nlml, double* grad, int* status) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (nhyp != m->nhyp)
+    return set_err(MFGP_ERR_ARG, "Hyperparameters must be of length 4 (single-fidelity) or 9 (multi-fidelity)");
+  if (S < 0) return set_err(MFGP_ERR_ARG, "S must be >= 0");
+  if (S == 0) return MFGP_OK;
+  if (!hyps) return set_err(MFGP_ERR_ARG, "null hyps");
+  if (!nlml) return set_err(MFGP_ERR_ARG, "null output");
+  mfgp_ctx* c = m->ctx;
+  const int64_t N = m->NL + m->NH;
+  if (N == 0) {   // empty data: every term is an empty sum
+    for (int s = 0; s < S; ++s) nlml[s] = 0.0;
+    if (grad)
+      for (int64_t e = 0; e < (int64_t)S * nhyp; ++e) grad[e] = 0.0;
+    if (status)
+      for (int s = 0; s < S; ++s) status[s] = 0;
+    return MFGP_OK;
+  }
+  // the leading dimension of mfgp_nlml's scratch model (ensure_cap of N rows)
+  const int64_t ld = round_up(std::max<int64_t>(N, 63) + 1, NB), np = nlml_partials(N);
+  const int64_t per = nlml_member_bytes(ld, np, grad != nullptr);
+  int64_t C = c->nlml_chunk > 0 ? c->nlml_chunk : std::max<int64_t>(1, (int64_t)NLML_BATCH_SCRATCH / per);
+  C = std::min<int64_t>({C, MAXB, S});
+  const NlmlLayout l = nlml_layout(ld, np, C, grad != nullptr);
+  if ((rc = ensure_nlml_scratch(c, l))) return rc;
+  if ((rc = ensure_h_status(c, (size_t)C))) return rc;
+  double* const dv = c->nb_dev;
+  int* const dst = reinterpret_cast<int*>(dv + l.o_st);
+  const double* const hb = c->nb_host;
+  const double nan = std::nan("");
+  int first_bad = 0;
+  for (int s0 = 0; s0 < S; s0 += (int)C) {
+    const int cnt = (int)std::min<int64_t>(C, S - s0);
+    int slot;
+    GPDesc* hd = acquire_slot(c, slot, rc);
+    if (!hd) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      mfgp_model t;   // a scratch factor of K(hyps[s0 + i]) over the caller's rows (a descriptor's worth of it)
+      t.ctx = c;
+      t.kind = m->kind;
+      t.dtype = MFGP_F64;
+      t.nhyp = nhyp;
+      std::memcpy(t.hyp, hyps + (size_t)(s0 + i) * nhyp, sizeof(double) * nhyp);
+      t.jitter = m->jitter;
+      t.NL = m->NL;
+      t.NH = m->NH;
+      t.cap = ld - 1;
+      t.ld = ld;
+      t.X = m->X;
+      t.y = m->y;
+      t.A = dv + l.o_A + (int64_t)i * ld * ld;
+      t.Linv = dv + l.o_Li + (int64_t)i * (ld / NB) * TILE;
+      t.zv = dv + l.o_zv + (int64_t)i * ld;
+      t.status = dst + i;
+      fill_desc(hd[i], &t);
+    }
+    const GPDesc* dd = nullptr;
+    if ((rc = upload_slot(c, slot, cnt, &dd))) return rc;
+    if ((rc = enqueue_factor(c, dd, hd, cnt))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_status, dst, sizeof(int) * cnt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(launch_nlml_value(dd, cnt, dv + l.o_val, c->stream));
+    if (grad)
+      HIP_TRY(launch_nlml_grad_batch(dd, cnt, N, dv + l.o_Xi, dv + l.o_Kv, dv + l.o_al, dv + l.o_part, ld * ld, ld, np,
+                                     c->stream));
+    if ((rc = release_slot(c, slot))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->nb_host + l.h_val, dv + l.o_val, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost,
+                           c->stream));
+    if (grad) {
+      HIP_TRY(hipMemcpyAsync(c->nb_host + l.h_part, dv + l.o_part, sizeof(double) * np * cnt, hipMemcpyDeviceToHost,
+                             c->stream));
+      HIP_TRY(hipMemcpyAsync(c->nb_host + l.h_al, dv + l.o_al, sizeof(double) * ld * cnt, hipMemcpyDeviceToHost,
+                             c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i, st = c->h_status[i];
+      double* const g = grad ? grad + (size_t)s * nhyp : nullptr;
+      if (st == INT_MAX) {
+        nlml_finish(m, hyps + (size_t)s * nhyp, N, hb + l.h_val + 2 * i, hb + l.h_part + (int64_t)i * np, np,
+                    hb + l.h_al + (int64_t)i * ld, nlml + s, g);
+        if (status) status[s] = 0;
+        continue;
+      }
+      if (st <= 0) return status_error(st);   // (no order of a leading minor: a device failure)
+      // not positive definite (the reference's cholesky raising, gp:101 / 380): this member only
+      nlml[s] = nan;
+      if (g)
+        for (int p = 0; p < nhyp; ++p) g[p] = nan;
+      if (status) status[s] = st;
+      if (!first_bad) first_bad = st;
     }
   }
-  return done(MFGP_OK);
+  if (!status && first_bad) return status_error(first_bad);
+  return MFGP_OK;
 }
 
 int mfgp_batch_append_predict(mfgp_model** models, int count, const double* X, const double* y, const int64_t* k,

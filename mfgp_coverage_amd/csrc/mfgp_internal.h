@@ -293,6 +293,11 @@ hipError_t launch_look_query(const LookArgs& a, hipStream_t s);
 hipError_t launch_nlml_value(const GPDesc* d, int count, double* out, hipStream_t s);
 hipError_t launch_nlml_grad(const GPDesc* d, int64_t N, double* Xi, double* Kv, double* alpha, double* part,
                             hipStream_t s);
+// the same for `count` GPs of N rows (grid (.., members)): member b on d[b], Xi / Kv +
+// b mstride, alpha + b astride, part + b pstride; a member whose status word is not
+// INT_MAX is skipped
+hipError_t launch_nlml_grad_batch(const GPDesc* d, int count, int64_t N, double* Xi, double* Kv, double* alpha,
+                                  double* part, int64_t mstride, int64_t astride, int64_t pstride, hipStream_t s);
 int64_t nlml_partials(int64_t N);
 hipError_t launch_choi_select(const GPDesc* d, double threshold, double* points, int64_t max_points,
                               hipStream_t s);

@@ -14,7 +14,11 @@
 //   k_nlml_grad   per lower tile: W = K^-1 - a a^T times every dK/dh (the SE
 //                 kernel's derivatives in the reference's operation order), reduced
 // The mean terms a^T dr/dh are O(N) and summed on the host.
+// mfgp_nlml_batch runs the same kernels for many hyperparameter vectors over one
+// data set, the member in blockIdx.y (k_nlml_value: blockIdx.x), one launch each.
 #include <hip/hip_runtime.h>
+
+#include <climits>
 
 #include "mfgp_device.h"
 #include "mfgp_internal.h"
@@ -77,10 +81,25 @@ __device__ __forceinline__ void store_acc_cm(const Acc& acc, double* __restrict_
         G[(c0 + acc_col(wn, nt, r)) * ld + r0 + acc_row(wm, mt, q, v)] = scale * acc.c[mt][nt][v];
 }
 
+// The gradient kernels below (k_trinv, k_kinv, k_alpha, k_nlml_grad) come in two
+// forms of one body. BATCH = false: the one GP descs[0] (mfgp_nlml). BATCH = true:
+// grid (.., members), member b = blockIdx.y works on descs[b] and on its own slice
+// of Xi / Kv / alpha / part (b strides on); a member whose factor failed (its
+// status word is not INT_MAX) is skipped. A member's arithmetic is the single
+// form's, tile product for tile product, whatever the other members are.
+template <bool BATCH>
+__device__ __forceinline__ bool nlml_member_live(const GPDesc& d) {
+  return !BATCH || *d.status == INT_MAX;
+}
+
 // X = L^-1 (lower, block rows/columns of 64). Block column J per workgroup:
 //   X_JJ = Linv_JJ;   X_IJ = Linv_II * (-(sum_{K=J}^{I-1} L_IK X_KJ))  for I > J.
-__global__ __launch_bounds__(NT) void k_trinv(const GPDesc* __restrict__ descs, double* __restrict__ Xi) {
-  const GPDesc& d = descs[0];
+template <bool BATCH>
+__global__ __launch_bounds__(NT) void k_trinv(const GPDesc* __restrict__ descs, double* __restrict__ Xi_,
+                                              int64_t mstride) {
+  const GPDesc& d = descs[BATCH ? blockIdx.y : 0];
+  if (!nlml_member_live<BATCH>(d)) return;
+  double* __restrict__ Xi = Xi_ + (BATCH ? (int64_t)blockIdx.y * mstride : 0);
   const int64_t ld = d.ld, nbr = nblocks_rows(d.N);
   const int64_t J = blockIdx.x;
   if (J >= nbr) return;
@@ -260,9 +279,13 @@ __global__ __launch_bounds__(NT) void k_trinv_lvl(const GPDesc* __restrict__ des
 }
 
 // K^-1 = X^T X over the real rows (k < N): tile (I, J), I >= J, sums K >= I.
-__global__ __launch_bounds__(NT) void k_kinv(const GPDesc* __restrict__ descs, const double* __restrict__ Xi,
-                                             double* __restrict__ Kv) {
-  const GPDesc& d = descs[0];
+template <bool BATCH>
+__global__ __launch_bounds__(NT) void k_kinv(const GPDesc* __restrict__ descs, const double* __restrict__ Xi_,
+                                             double* __restrict__ Kv_, int64_t mstride) {
+  const GPDesc& d = descs[BATCH ? blockIdx.y : 0];
+  if (!nlml_member_live<BATCH>(d)) return;
+  const double* __restrict__ Xi = Xi_ + (BATCH ? (int64_t)blockIdx.y * mstride : 0);
+  double* __restrict__ Kv = Kv_ + (BATCH ? (int64_t)blockIdx.y * mstride : 0);
   const int64_t ld = d.ld, N = d.N, nbr = nblocks_rows(N);
   int I, J;
   tri_index(blockIdx.x, I, J);
@@ -282,9 +305,13 @@ __global__ __launch_bounds__(NT) void k_kinv(const GPDesc* __restrict__ descs, c
 }
 
 // a = X^T z over the real rows: a_j = sum_{k >= j, k < N} X[k][j] z_k.
-__global__ __launch_bounds__(NT) void k_alpha(const GPDesc* __restrict__ descs, const double* __restrict__ Xi,
-                                              double* __restrict__ alpha) {
-  const GPDesc& d = descs[0];
+template <bool BATCH>
+__global__ __launch_bounds__(NT) void k_alpha(const GPDesc* __restrict__ descs, const double* __restrict__ Xi_,
+                                              double* __restrict__ alpha_, int64_t mstride, int64_t astride) {
+  const GPDesc& d = descs[BATCH ? blockIdx.y : 0];
+  if (!nlml_member_live<BATCH>(d)) return;
+  const double* __restrict__ Xi = Xi_ + (BATCH ? (int64_t)blockIdx.y * mstride : 0);
+  double* __restrict__ alpha = alpha_ + (BATCH ? (int64_t)blockIdx.y * astride : 0);
   const int64_t ld = d.ld, N = d.N;
   const int64_t j = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -298,10 +325,16 @@ __global__ __launch_bounds__(NT) void k_alpha(const GPDesc* __restrict__ descs, 
 
 // 1/2 sum_ij W_ij dK_ij/dh over the lower triangle (off-diagonal pairs twice).
 // SF hyp [m, s, l, sn]; MF hyp [mL, sL, lL, mH, sH, lH, rho, snL, snH] (log-scaled).
-__global__ __launch_bounds__(NT) void k_nlml_grad(const GPDesc* __restrict__ descs, const double* __restrict__ Kv,
-                                                  const double* __restrict__ alpha, double* __restrict__ part) {
+template <bool BATCH>
+__global__ __launch_bounds__(NT) void k_nlml_grad(const GPDesc* __restrict__ descs, const double* __restrict__ Kv_,
+                                                  const double* __restrict__ alpha_, double* __restrict__ part_,
+                                                  int64_t mstride, int64_t astride, int64_t pstride) {
 #pragma clang fp contract(off)
-  const GPDesc& d = descs[0];
+  const GPDesc& d = descs[BATCH ? blockIdx.y : 0];
+  if (!nlml_member_live<BATCH>(d)) return;
+  const double* __restrict__ Kv = Kv_ + (BATCH ? (int64_t)blockIdx.y * mstride : 0);
+  const double* __restrict__ alpha = alpha_ + (BATCH ? (int64_t)blockIdx.y * astride : 0);
+  double* __restrict__ part = part_ + (BATCH ? (int64_t)blockIdx.y * pstride : 0);
   const int64_t ld = d.ld, N = d.N, NL = d.NL, nbr = nblocks_rows(N);
   const Hyp& h = d.hf;
   int I, J;
@@ -390,10 +423,30 @@ hipError_t launch_nlml_grad(const GPDesc* d, int64_t N, double* Xi, double* Kv, 
   const int64_t nbr = nblocks_rows(N);
   if (nbr <= 0) return hipSuccess;
   const int64_t ntri = nbr * (nbr + 1) / 2;
-  hipLaunchKernelGGL(k_trinv, dim3((unsigned)nbr), dim3(NT), 0, s, d, Xi);
-  hipLaunchKernelGGL(k_kinv, dim3((unsigned)ntri), dim3(NT), 0, s, d, Xi, Kv);
-  hipLaunchKernelGGL(k_alpha, dim3((unsigned)((N + NT / 64 - 1) / (NT / 64))), dim3(NT), 0, s, d, Xi, alpha);
-  hipLaunchKernelGGL(k_nlml_grad, dim3((unsigned)ntri), dim3(NT), 0, s, d, Kv, alpha, part);
+  const int64_t z = 0;
+  hipLaunchKernelGGL(k_trinv<false>, dim3((unsigned)nbr), dim3(NT), 0, s, d, Xi, z);
+  hipLaunchKernelGGL(k_kinv<false>, dim3((unsigned)ntri), dim3(NT), 0, s, d, Xi, Kv, z);
+  hipLaunchKernelGGL(k_alpha<false>, dim3((unsigned)((N + NT / 64 - 1) / (NT / 64))), dim3(NT), 0, s, d, Xi, alpha, z,
+                     z);
+  hipLaunchKernelGGL(k_nlml_grad<false>, dim3((unsigned)ntri), dim3(NT), 0, s, d, Kv, alpha, part, z, z, z);
+  return hipGetLastError();
+}
+
+// The same for `count` GPs of N rows each (mfgp_nlml_batch): one launch of each
+// kernel, member b on descs[b], Xi + b mstride, Kv + b mstride, alpha + b astride
+// and part + b pstride.
+hipError_t launch_nlml_grad_batch(const GPDesc* d, int count, int64_t N, double* Xi, double* Kv, double* alpha,
+                                  double* part, int64_t mstride, int64_t astride, int64_t pstride, hipStream_t s) {
+  const int64_t nbr = nblocks_rows(N);
+  if (nbr <= 0 || count <= 0) return hipSuccess;
+  const int64_t ntri = nbr * (nbr + 1) / 2;
+  const unsigned nb = (unsigned)count;
+  hipLaunchKernelGGL(k_trinv<true>, dim3((unsigned)nbr, nb), dim3(NT), 0, s, d, Xi, mstride);
+  hipLaunchKernelGGL(k_kinv<true>, dim3((unsigned)ntri, nb), dim3(NT), 0, s, d, Xi, Kv, mstride);
+  hipLaunchKernelGGL(k_alpha<true>, dim3((unsigned)((N + NT / 64 - 1) / (NT / 64)), nb), dim3(NT), 0, s, d, Xi, alpha,
+                     mstride, astride);
+  hipLaunchKernelGGL(k_nlml_grad<true>, dim3((unsigned)ntri, nb), dim3(NT), 0, s, d, Kv, alpha, part, mstride, astride,
+                     pstride);
   return hipGetLastError();
 }
 

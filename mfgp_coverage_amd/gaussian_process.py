@@ -26,6 +26,10 @@ Differences from the reference, all on the output side of the contract:
   1e-6 * k**).
 * ``likelihood``/``train`` (gp:81-119, 344-399) run on the GPU with an analytic
   gradient in place of autograd (``likelihood_and_grad``).
+  ``likelihood_batch`` / ``likelihood_and_grad_batch`` evaluate many hyperparameter
+  vectors in one set of launches, and ``train(n_restarts=..)`` / ``train(starts=..)``
+  runs L-BFGS-B from several starts in lockstep on them (no callback prints then);
+  ``train()`` alone is the reference's.
 * ``draw_prior_samples`` / ``draw_posterior_samples`` (gp:180-217) draw from the
   device's covariance; the posterior draws are of ``predict``'s posterior (the
   reference's omit the prior mean and do not centre y).
@@ -335,12 +339,76 @@ class _DeviceGP:
         """gaussian_process.py:219-227 / 483-491."""
         print("Log likelihood {}".format(self.likelihood(params)))
 
-    def train(self):
-        """gaussian_process.py:108-119 / 388-399: L-BFGS-B on the NLML with its gradient."""
-        from scipy.optimize import minimize
-        result = minimize(self.likelihood_and_grad, self.hyp, jac=True, method="L-BFGS-B",
-                          callback=self.callback)
-        self.hyp = result.x
+    def _hyps_arg(self, hyps):
+        h = np.ascontiguousarray(np.asarray(hyps, dtype=np.float64))
+        if h.ndim != 2 or h.shape[1] != self._hyp_vec().shape[0]:
+            raise TypeError("Hyperparameters must be of length 4 (single-fidelity) or 9 (multi-fidelity)")
+        return h
+
+    def likelihood_batch(self, hyps):
+        """likelihood for every row of hyps [S, nhyp] in one set of launches
+        (mfgp_nlml_batch): values [S], row s with the bits of likelihood(hyps[s]). A row
+        that is not positive definite raises LinAlgError, as likelihood does."""
+        self._sync_data()
+        return self._dev().nlml_batch(self._hyps_arg(hyps))
+
+    def likelihood_and_grad_batch(self, hyps):
+        """(values [S], gradients [S, nhyp]): likelihood_and_grad for every row of hyps."""
+        self._sync_data()
+        return self._dev().nlml_batch(self._hyps_arg(hyps), grad=True)
+
+    def train(self, n_restarts=0, starts=None, scale=1.0, seed=None):
+        """gaussian_process.py:108-119 / 388-399: L-BFGS-B on the NLML with its gradient.
+
+        With n_restarts > 0 or explicit starts [S, nhyp] (not in the reference) it trains
+        from several starts in lockstep on the batched likelihood
+        (training.lockstep_minimize on mfgp_nlml_batch): self.hyp followed by n_restarts
+        draws of self.hyp + scale * N(0, 1) from np.random.default_rng(seed), or the given
+        starts as they are. Each start's run is the solo L-BFGS-B run from it. self.hyp
+        becomes the x of the lowest final NLML among the starts that did not fail (a tie:
+        the earliest); self.train_runs holds one record per start (x0, x, fun, nit, nfev,
+        success, message). A start that reaches a point that is not positive definite
+        ends as failed; if every start fails, LinAlgError is raised and self.hyp stays.
+        There is no per-iteration callback in this mode (it would cost one more device
+        evaluation per iteration)."""
+        if not n_restarts and starts is None:
+            from scipy.optimize import minimize
+            result = minimize(self.likelihood_and_grad, self.hyp, jac=True, method="L-BFGS-B",
+                              callback=self.callback)
+            self.hyp = result.x
+            return
+        from .training import lockstep_minimize
+        if starts is None:
+            h0 = self._hyp_vec()
+            rng = np.random.default_rng(seed)
+            starts = np.vstack([h0] + [h0 + scale * rng.standard_normal(h0.shape[0]) for _ in range(int(n_restarts))])
+        starts = self._hyps_arg(starts).copy()
+        self._sync_data()
+        model = self._dev()
+
+        def batch_fun(xs):
+            v, g, st = model.nlml_batch(np.vstack(xs), grad=True, status=True)
+            return [(float(v[i]), g[i].copy()) if st[i] == 0 else
+                    np.linalg.LinAlgError(f"Matrix is not positive definite (leading minor of order {int(st[i])})")
+                    for i in range(len(xs))]
+
+        results = lockstep_minimize(batch_fun, starts)
+        runs, best = [], None
+        for x0, r in zip(starts, results):
+            if isinstance(r, BaseException):
+                if not isinstance(r, np.linalg.LinAlgError):
+                    raise r
+                runs.append({"x0": x0, "x": None, "fun": float("nan"), "nit": 0, "nfev": 0, "success": False,
+                             "message": str(r)})
+                continue
+            runs.append({"x0": x0, "x": r.x, "fun": float(r.fun), "nit": int(r.nit), "nfev": int(r.nfev),
+                         "success": bool(r.success), "message": r.message})
+            if best is None or runs[-1]["fun"] < best["fun"]:
+                best = runs[-1]
+        self.train_runs = runs
+        if best is None:
+            raise np.linalg.LinAlgError("train: every start reached a point that is not positive definite")
+        self.hyp = best["x"].copy()
 
     def __deepcopy__(self, memo):
         new = self.__class__.__new__(self.__class__)
