@@ -32,6 +32,7 @@ extern "C" {
 #define MFGP_ERR_ARG 2      /* bad argument: TypeError/ValueError (simulator.py:366, 652)     */
 #define MFGP_ERR_DEVICE 3   /* HIP runtime error: RuntimeError                                */
 #define MFGP_ERR_NO_V 4     /* mfgp_cov_block: the resident V does not cover the model's rows   */
+#define MFGP_ERR_NO_LATTICE 5   /* the grid is not a lattice, or a training row is not one of its cells */
 
 #define MFGP_SF 0           /* SFGP, gaussian_process.py:23-268, hyp [mu, s2, L, noise]              */
 #define MFGP_MF 1           /* MFGP, gaussian_process.py:271-578, hyp [mu_lo,s2_lo,L_lo,mu_hi,s2_hi,
@@ -250,6 +251,54 @@ int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq,
                const double* XL_new, int64_t nl_new, const double* XH_new, int64_t nh_new,
                double* mu, double* var0, double* var, double* cov, int64_t ldc);
 
+/* Pathwise (Matheron) joint samples on the whole grid, at a cost linear in M: a prior
+ * sample corrected through the data,
+ *   f_post(grid) = m_H + f_prior(grid) + psi K^-1 (y - m - f_prior(X) - eps)
+ *                = m_H + f_prior(grid) + V^T L^-1 r,
+ *   r = (y - m) - f_prior(X) - sqrt(noise_fid + jitter) eps,
+ * whose covariance is k** - psi K^-1 psi^T and whose mean is mfgp_predict's mu. The grid
+ * must be a lattice and every training row one of its cells: the SE kernel separates
+ * over the two axes, so sqrt(s) Ax Z Ay^T with Ax Ax^T = Kx, Ay Ay^T = Ky has the prior
+ * covariance (an MF model: two independent fields u_L and delta, hifi = rho u_L + delta,
+ * a lofi row sees u_L). The axis factors are diagonally pivoted Cholesky factors in fp64
+ * on the host, of the unit-diagonal axis Gram exp(-(a_i / l - a_j / l)^2 / 2), stopped
+ * when the largest remaining diagonal entry is <= 2^-50 (|A A^T - K| is bounded by that
+ * plus rounding), stored n x rank. A sample takes nz = sum over fields rx ry + N normals. */
+#define MFGP_SAMPLE_PRIOR 1     /* zero-mean draws of the hifi prior k** (no data, no factor needed) */
+
+/* Host only, no device work: the pivoted-Cholesky factor of one axis. A is [n][n]
+ * row-major, columns >= *rank zero. MFGP_ERR_ARG: a NULL pointer, n < 0, a length scale
+ * that is not positive and finite, an axis value that is not finite. */
+int mfgp_sample_axis_factor(const double* axis, int n, double lengthscale, double* A, int* rank);
+
+/* dims[0..n): {nz, M, N, fields, rx0, ry0, rx1, ry1}; n <= 8. Settles the model as
+ * mfgp_sample_posterior does (with MFGP_SAMPLE_PRIOR: nz without N, N = 0, nothing settled). */
+int mfgp_sample_dims(mfgp_model* m, int64_t* dims, int n, int flags);
+
+/* normals [S][ldz] (ldz >= nz): per sample field 0's rx0*ry0 block (row-major, x index
+ * outer), field 1's, then one normal per training row in model order. out [S][ldo]
+ * (ldo >= M), a sample's cells contiguous in grid order. Host or device pointers.
+ * Every argument is checked before anything is enqueued: S < 0, ldz < nz, ldo < M, NULL
+ * pointers with S > 0, non-finite normals in a host buffer, a model without a grid or an
+ * MFGP_F32 model (as mfgp_cov_block) return MFGP_ERR_ARG, launch nothing and leave the
+ * model as it was. S == 0: MFGP_OK, nothing written. The call first brings the model to
+ * the state mfgp_predict leaves (a pending or deferred append, new hyperparameters or a
+ * new grid are settled there, MFGP_ERR_NOT_PD surfaces as there); if V still does not
+ * cover the N rows it returns MFGP_ERR_NO_V. A grid that is not a lattice, or a training
+ * row that is no cell of it, returns MFGP_ERR_NO_LATTICE. flags: MFGP_SAMPLE_PRIOR = the
+ * noise block of the normals is not read and nz excludes N; N = 0 without it gives
+ * m_H + prior. Of the model the call changes only its sample record (the axis factors,
+ * keyed by the model's serial, and the rows' lattice indices; allocated at the first
+ * call, freed with the model, not cloned) and the counters sample_solve / sample_gemm of
+ * mfgp_model_stats: rows, serial, grid, V, F and the lattice tables, the resident
+ * posterior, the kept predict result and the path counters stay, so a predict before and
+ * after returns the same bits by the same path. S > 64 runs in chunks of 64 (k_sample_t,
+ * k_sample_field, k_sample_resid, k_sample_solve, k_sample_gemm per chunk). A sample's
+ * bits depend only on its own nz normals: not on S, on its position, on the other
+ * samples or on the chunking, and two calls agree bit for bit. */
+int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64_t ldz,
+                          double* out, int64_t ldo, int flags);
+
 /* Sizes and state readers (the Python mirror's .X/.L attributes). */
 int64_t mfgp_model_n(const mfgp_model* m);      /* N = NL + NH */
 int64_t mfgp_model_nl(const mfgp_model* m);
@@ -265,7 +314,8 @@ int64_t mfgp_model_m(const mfgp_model* m);
  * resident posterior because the model appended nothing (k_post_copy), eager
  * appends of one GP that returned at the launch's published L22 verdict
  * (mfgp_append above), k_look_border launches and k_look_query launches of
- * mfgp_query (index 14 look_border, 15 look_query)}; n <= 16. */
+ * mfgp_query (index 14 look_border, 15 look_query), k_sample_solve and k_sample_gemm
+ * launches of mfgp_sample_posterior (index 16 sample_solve, 17 sample_gemm)}; n <= 18. */
 int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n);
 /* Copy the lower Cholesky factor L [N,N] (row-major, zeros above the diagonal). */
 int mfgp_get_factor(mfgp_model* m, double* L_out);

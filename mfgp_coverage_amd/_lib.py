@@ -15,8 +15,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFGP_LIB") or os.path.join(HERE, "libmfgp_hip.so")
 
-OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE, ERR_NO_V = 0, 1, 2, 3, 4
+OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE, ERR_NO_V, ERR_NO_LATTICE = 0, 1, 2, 3, 4, 5
 COV_PRIOR = 1
+SAMPLE_PRIOR = 1
 LOOK_MAX = 64   # prospective points per query (MFGP_LOOK_MAX)
 QueryResult = collections.namedtuple("QueryResult", ("mu", "var0", "var", "cov"))
 SF, MF = 0, 1
@@ -83,6 +84,11 @@ SIGNATURES = {
     "mfgp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "mfgp_sample_axis_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_int)]),
+    "mfgp_sample_dims": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, ctypes.c_int, ctypes.c_int]),
+    "mfgp_sample_posterior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
     "mfgp_model_serial": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "mfgp_release_view": (ctypes.c_int, [ctypes.c_void_p]),
     "mfgp_view_max": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_int64_p, ctypes.POINTER(ctypes.c_int)]),
@@ -133,10 +139,16 @@ def lib():
     return _lib
 
 
+class NoLatticeError(ValueError):
+    """MFGP_ERR_NO_LATTICE: the grid is not a lattice, or a training row is not one of its cells."""
+
+
 def check(rc):
     if rc == OK:
         return
     msg = lib().mfgp_last_error().decode(errors="replace")
+    if rc == ERR_NO_LATTICE:
+        raise NoLatticeError(msg)
     if rc == ERR_NOT_PD:
         raise np.linalg.LinAlgError(msg)
     if rc == ERR_ARG:
@@ -441,6 +453,56 @@ class Model:
                                op(o_mu), op(o_v0), op(o_v), op(o_c), ldc))
         return QueryResult(o_mu, o_v0, o_v, None if o_c is None else o_c[:, :n])
 
+    SAMPLE_DIMS = ("nz", "M", "N", "fields", "rx0", "ry0", "rx1", "ry1")
+
+    def sample_dims(self, prior=False):
+        """{nz, M, N, fields, rx0, ry0, rx1, ry1} of sample() (mfgp_sample_dims): nz normals
+        per sample = field 0's rx0 x ry0 block, field 1's rx1 x ry1 (MF), then one per
+        training row (none with prior). Settles the model as sample() does."""
+        out = (ctypes.c_int64 * 8)()
+        check(lib().mfgp_sample_dims(self.handle, out, 8, SAMPLE_PRIOR if prior else 0))
+        return dict(zip(self.SAMPLE_DIMS, (int(v) for v in out)))
+
+    def sample(self, normals, prior=False, out=None, ldz=None, ldo=None, S=None):
+        """Pathwise joint samples on the whole lattice grid (mfgp_sample_posterior): [S, M],
+        row s the sample of normals[s] ([S, >= nz] float64 standard normals, sample_dims()).
+        prior: zero-mean draws of the hifi prior (no data involved). out: a host float64
+        matrix [>= S, >= M] to fill in place (its row stride is the leading dimension).
+        With normals / out as integer device addresses give S and ldz / ldo (returns None
+        for a device out). A sample's bits depend on its own normals only."""
+        L = lib()
+        M = L.mfgp_model_m(self.handle)
+        flags = SAMPLE_PRIOR if prior else 0
+        if isinstance(normals, (int, np.integer)):
+            if S is None or ldz is None:
+                raise ValueError("device normals need S and ldz")
+            zp, S, ldz = ctypes.c_void_p(int(normals)), int(S), int(ldz)
+        else:
+            z = np.asarray(normals, dtype=np.float64)
+            if z.ndim != 2:
+                raise ValueError("normals must be [S, >= nz]")
+            if z.strides[1] != 8 or z.strides[0] % 8 or z.strides[0] < 8 * z.shape[1]:
+                z = np.ascontiguousarray(z)
+            S = z.shape[0] if S is None else int(S)
+            if S > z.shape[0]:
+                raise ValueError("S exceeds the rows of normals")
+            ldz = (z.strides[0] // 8 if z.shape[0] > 1 else z.shape[1]) if ldz is None else int(ldz)
+            zp = ctypes.c_void_p(z.ctypes.data)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.float64 or out.ndim != 2 or out.strides[1] != 8 or out.strides[0] % 8 or \
+                    out.shape[0] < S or not out.flags.writeable:
+                raise ValueError("out must be a writable row-major float64 matrix of at least [S] rows")
+            ld = (out.strides[0] // 8 if out.shape[0] > 1 else out.shape[1]) if ldo is None else int(ldo)
+            check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(out.ctypes.data), ld, flags))
+            return out[:S, :M]
+        if out is not None:
+            check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(int(out)),
+                                          int(M if ldo is None else ldo), flags))
+            return None
+        buf = np.empty((S, max(M, 1)), dtype=np.float64)
+        check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(buf.ctypes.data), max(M, 1), flags))
+        return buf[:, :M]
+
     def serial(self):
         """The model's posterior serial (mfgp_model_serial): changes whenever its rows,
         hyperparameters, jitter or grid change, and never repeats."""
@@ -471,12 +533,13 @@ class Model:
         (k_lat_gemm2); {post_copy}: batch predicts served from the resident posterior
         because the model appended nothing (k_post_copy); {early_pd}: eager appends that
         returned at the launch's published L22 verdict (mfgp_append, one GP);
-        {look_border, look_query}: the k_look_border / k_look_query launches of query()."""
-        out = (ctypes.c_int64 * 16)()
-        check(lib().mfgp_model_stats(self.handle, out, 16))
+        {look_border, look_query}: the k_look_border / k_look_query launches of query();
+        {sample_solve, sample_gemm}: the k_sample_solve / k_sample_gemm launches of sample()."""
+        out = (ctypes.c_int64 * 18)()
+        check(lib().mfgp_model_stats(self.handle, out, 18))
         keys = ("factor_rows", "v_rows", "full_factor", "inc_factor", "full_predict", "vstream",
                 "lattice_nx", "lattice_ny", "lattice", "lattice_virtual", "lattice_arg", "lattice_g2",
-                "post_copy", "early_pd", "look_border", "look_query")
+                "post_copy", "early_pd", "look_border", "look_query", "sample_solve", "sample_gemm")
         return dict(zip(keys, (int(v) for v in out)))
 
     def sample_points(self, threshold, max_points):
@@ -519,6 +582,18 @@ class Model:
 
     def truncate(self, n_keep_hifi):
         check(lib().mfgp_truncate(self.handle, int(n_keep_hifi)))
+
+
+def sample_axis_factor(axis, lengthscale):
+    """mfgp_sample_axis_factor (host only): (A [n, rank], rank), the pivoted-Cholesky
+    factor of the unit-diagonal SE Gram of the axis values at that length scale."""
+    a = np.ascontiguousarray(np.asarray(axis, dtype=np.float64).reshape(-1))
+    n = a.shape[0]
+    A = np.zeros((n, n), dtype=np.float64)
+    r = ctypes.c_int(0)
+    check(lib().mfgp_sample_axis_factor(ctypes.c_void_p(a.ctypes.data), n, float(lengthscale),
+                                        ctypes.c_void_p(A.ctypes.data), ctypes.byref(r)))
+    return A[:, :r.value].copy(), int(r.value)
 
 
 def batch_append_predict(models, X, y, k, mu_ptr, var_ptr, asynchronous=False, vmax_ptr=None, vargmax_ptr=None):

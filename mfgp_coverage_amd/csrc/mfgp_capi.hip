@@ -187,6 +187,24 @@ struct mfgp_look_rec {
   std::vector<double> key;   // the P rows (x, y), then their fidelities
 };
 
+// The sample record of a model (mfgp_sample_posterior): the pivoted-Cholesky factors of
+// the lattice axes' Gram matrices per field, keyed by the model's serial, and the
+// lattice indices of its training rows.
+struct mfgp_sample_rec {
+  bool valid = false;        // the axis factors below belong to `serial`
+  uint64_t serial = 0;
+  int fields = 0, nx = 0, ny = 0;
+  int rx[2] = {0, 0}, ry[2] = {0, 0};
+  double* fac = nullptr;     // device: per field Ax [nx][rx] | AyT [ry][ny]
+  size_t fac_n = 0;          // doubles allocated
+  size_t off_ax[2] = {0, 0}, off_ay[2] = {0, 0};
+  int* lidx = nullptr;       // device [lidx_cap]: px | (py << 16) per training row
+  int64_t lidx_cap = 0;
+  bool lidx_valid = false;   // lidx holds the N rows of `lidx_serial`
+  uint64_t lidx_serial = 0;
+  int64_t off_row = -1;      // the first training row that is no cell of the lattice, or -1
+};
+
 struct mfgp_model {
   mfgp_ctx* ctx = nullptr;
   int* gate_dev = nullptr;  // device gate of every step of this model (the planners' loops: 0 = skip)
@@ -250,6 +268,8 @@ struct mfgp_model {
   int64_t n_early_pd = 0;      // eager appends that returned at the launch's published L22 verdict
   mfgp_look_rec* look = nullptr;   // look-ahead record (allocated by the first mfgp_query, not cloned)
   int64_t n_look_border = 0, n_look_query = 0;   // k_look_border / k_look_query launches
+  mfgp_sample_rec* samp = nullptr;   // sample record (allocated by the first mfgp_sample_*, not cloned)
+  int64_t n_sample_solve = 0, n_sample_gemm = 0;   // k_sample_solve / k_sample_gemm launches
   unsigned* csr = nullptr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
   int64_t csr_n = 0;           // (bytes)
   // state generation: a new factor from scratch, a new grid or new hyperparameters
@@ -1797,6 +1817,11 @@ void mfgp_model_destroy(mfgp_model* m) {
     if (m->look->pfid) (void)hipFree(m->look->pfid);
     delete m->look;
   }
+  if (m->samp) {
+    if (m->samp->fac) (void)hipFree(m->samp->fac);
+    if (m->samp->lidx) (void)hipFree(m->samp->lidx);
+    delete m->samp;
+  }
   free_lat(m);
   delete m;
 }
@@ -2446,6 +2471,327 @@ int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq, const double* XL_new
   return MFGP_OK;
 }
 
+// Pathwise samples (mfgp_sample.hip). The axis factor: a diagonally pivoted Cholesky
+// of the unit-diagonal axis Gram exp(-(a_i / l - a_j / l)^2 / 2), stopped when the
+// largest remaining diagonal entry is <= 2^-50. cols: rank columns of n entries each
+// (column k = the k-th pivot step; rows are not permuted, so cols cols^T = K up to the
+// positive semi-definite remainder).
+constexpr double SAMPLE_PIVOT_STOP = 0x1p-50;
+constexpr int SAMPLE_AXIS_MAX = 4096;              // lattice axis length the sampler serves
+constexpr size_t SAMPLE_T_MAX = size_t(1) << 30;   // bytes of the chunk's Ax Z scratch
+
+static int axis_factor(const double* axis, int n, double l, std::vector<double>& cols) {
+  cols.clear();
+  std::vector<double> t((size_t)n), d((size_t)n, 1.0);
+  std::vector<char> used((size_t)n, 0);
+  for (int i = 0; i < n; ++i) t[i] = axis[i] / l;
+  int rank = 0;
+  for (int k = 0; k < n; ++k) {
+    int p = -1;
+    double best = SAMPLE_PIVOT_STOP;
+    for (int i = 0; i < n; ++i)
+      if (!used[i] && d[i] > best) {
+        best = d[i];
+        p = i;
+      }
+    if (p < 0) break;
+    const double piv = std::sqrt(best);
+    cols.resize((size_t)(k + 1) * n);
+    double* c = cols.data() + (size_t)k * n;
+    for (int i = 0; i < n; ++i) {
+      if (used[i]) {
+        c[i] = 0.0;
+        continue;
+      }
+      if (i == p) {
+        c[i] = piv;
+        continue;
+      }
+      const double dx = t[i] - t[p];
+      double v = std::exp(-0.5 * (dx * dx));
+      for (int j = 0; j < k; ++j) v -= cols[(size_t)j * n + i] * cols[(size_t)j * n + p];
+      c[i] = v / piv;
+      d[i] -= c[i] * c[i];
+    }
+    used[p] = 1;
+    d[p] = 0.0;
+    rank = k + 1;
+  }
+  return rank;
+}
+
+int mfgp_sample_axis_factor(const double* axis, int n, double lengthscale, double* A, int* rank) {
+  if (n < 0 || (n > 0 && (!axis || !A)) || !rank)
+    return set_err(MFGP_ERR_ARG, "mfgp_sample_axis_factor: null pointer or negative n");
+  if (!(lengthscale > 0.0) || !std::isfinite(lengthscale))
+    return set_err(MFGP_ERR_ARG, "mfgp_sample_axis_factor: the length scale must be positive and finite");
+  if (!all_finite(axis, n)) return set_err(MFGP_ERR_ARG, "mfgp_sample_axis_factor: the axis values must be finite");
+  std::vector<double> cols;
+  const int r = axis_factor(axis, n, lengthscale, cols);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < n; ++k) A[(size_t)i * n + k] = k < r ? cols[(size_t)k * n + i] : 0.0;
+  *rank = r;
+  return MFGP_OK;
+}
+
+// The checks and the record every sample entry point shares, without any launch: the
+// model serves samples (fp64, a lattice grid within the sampler's sizes) and its sample
+// record holds the axis factors of the current serial.
+static int sample_record(mfgp_model* m, const char* who) {
+  if (m->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG, "%s: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model", who);
+  if (m->M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "%s: the model has no grid (mfgp_set_grid)", who);
+  const GridLattice& L = m->lat;
+  if (L.nx <= 0 || L.ny <= 0)
+    return set_err(MFGP_ERR_NO_LATTICE, "%s: the grid is not a lattice of two axes", who);
+  if (L.nx > SAMPLE_AXIS_MAX || L.ny > SAMPLE_AXIS_MAX)
+    return set_err(MFGP_ERR_ARG, "%s: lattice axes of at most %d values are supported (this grid's: %d x %d)", who,
+                   SAMPLE_AXIS_MAX, L.nx, L.ny);
+  if (!m->samp) m->samp = new mfgp_sample_rec();
+  mfgp_sample_rec* k = m->samp;
+  if (k->valid && k->serial == m->serial) return MFGP_OK;
+  mfgp_ctx* c = m->ctx;
+  k->valid = false;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<double> ax((size_t)L.nx), ay((size_t)L.ny);
+  HIP_TRY(hipMemcpy2D(ax.data(), sizeof(double), m->grid, sizeof(double) * 2 * L.sx, sizeof(double), L.nx,
+                      hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(ay.data(), sizeof(double), m->grid + 1, sizeof(double) * 2 * L.sy, sizeof(double), L.ny,
+                      hipMemcpyDeviceToHost));
+  const Hyp h = derive_hyp(m->kind, m->hyp, m->jitter);
+  const int fields = m->kind == MFGP_SF ? 1 : 2;
+  std::vector<double> host;
+  for (int f = 0; f < fields; ++f) {
+    const double l = f ? h.lH : h.lL;
+    if (!(l > 0.0) || !std::isfinite(l)) return set_err(MFGP_ERR_ARG, "%s: the length scales must be positive and finite", who);
+    std::vector<double> cx, cy;
+    k->rx[f] = axis_factor(ax.data(), L.nx, l, cx);
+    k->ry[f] = axis_factor(ay.data(), L.ny, l, cy);
+    k->off_ax[f] = host.size();   // Ax [nx][rx] row-major
+    host.resize(host.size() + (size_t)L.nx * k->rx[f]);
+    for (int i = 0; i < L.nx; ++i)
+      for (int a = 0; a < k->rx[f]; ++a) host[k->off_ax[f] + (size_t)i * k->rx[f] + a] = cx[(size_t)a * L.nx + i];
+    k->off_ay[f] = host.size();   // AyT [ry][ny]: the columns as they are
+    host.insert(host.end(), cy.begin(), cy.end());
+  }
+  if (fields == 1) k->rx[1] = k->ry[1] = 0;
+  if (host.size() > k->fac_n) {
+    if (k->fac) HIP_TRY(hipFree(k->fac));
+    k->fac = nullptr;
+    k->fac_n = 0;
+    HIP_TRY(hipMalloc(&k->fac, sizeof(double) * host.size()));
+    k->fac_n = host.size();
+  }
+  HIP_TRY(hipMemcpy(k->fac, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+  k->fields = fields;
+  k->nx = L.nx;
+  k->ny = L.ny;
+  k->serial = m->serial;
+  k->valid = true;
+  return MFGP_OK;
+}
+
+static int64_t sample_nz(const mfgp_model* m, bool prior) {
+  const mfgp_sample_rec* k = m->samp;
+  return (int64_t)k->rx[0] * k->ry[0] + (int64_t)k->rx[1] * k->ry[1] + (prior ? 0 : m->NL + m->NH);
+}
+
+// As mfgp_cov_block does: the state mfgp_predict leaves, with V over all N rows.
+static int sample_settle(mfgp_model* m, const char* who) {
+  int rc;
+  if (m->NL + m->NH == 0 || v_covers(m)) return MFGP_OK;
+  if ((rc = ensure_spec_out(m))) return rc;
+  m->spec_valid = false;
+  if ((rc = mfgp_predict(m, m->spec_out, m->spec_out + m->spec_cap))) return rc;
+  if (!v_covers(m))
+    return set_err(MFGP_ERR_NO_V, "%s: the resident V holds %lld of the model's %lld rows after a predict", who,
+                   (long long)m->v_n, (long long)(m->NL + m->NH));
+  return MFGP_OK;
+}
+
+// The lattice indices of the N training rows into the record (host search by exact
+// equality on the axis values, as the lattice step's tables do on the device).
+static int sample_lidx(mfgp_model* m, const char* who) {
+  mfgp_sample_rec* k = m->samp;
+  mfgp_ctx* c = m->ctx;
+  const int64_t N = m->NL + m->NH;
+  const GridLattice& L = m->lat;
+  if (!(k->lidx_valid && k->lidx_serial == m->serial)) {
+    k->lidx_valid = false;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<double> ax((size_t)L.nx), ay((size_t)L.ny), X((size_t)2 * N);
+    HIP_TRY(hipMemcpy2D(ax.data(), sizeof(double), m->grid, sizeof(double) * 2 * L.sx, sizeof(double), L.nx,
+                        hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(ay.data(), sizeof(double), m->grid + 1, sizeof(double) * 2 * L.sy, sizeof(double), L.ny,
+                        hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(X.data(), m->X, sizeof(double) * 2 * N, hipMemcpyDeviceToHost));
+    auto find = [](const std::vector<double>& a, double v) -> int {   // a strictly monotone, either way
+      const bool up = a.size() < 2 || a[1] > a[0];
+      int64_t lo = 0, hi = (int64_t)a.size() - 1;
+      while (lo <= hi) {
+        const int64_t mid = (lo + hi) / 2;
+        if (a[mid] == v) return (int)mid;
+        if ((a[mid] < v) == up) lo = mid + 1;
+        else hi = mid - 1;
+      }
+      return -1;
+    };
+    std::vector<int> li((size_t)N);
+    k->off_row = -1;
+    for (int64_t i = 0; i < N; ++i) {
+      const int px = find(ax, X[2 * i]), py = find(ay, X[2 * i + 1]);
+      li[i] = (px >= 0 && py >= 0) ? (px | (py << 16)) : -1;
+      if (li[i] < 0 && k->off_row < 0) k->off_row = i;
+    }
+    if (k->lidx_cap < N) {
+      if (k->lidx) HIP_TRY(hipFree(k->lidx));
+      k->lidx = nullptr;
+      k->lidx_cap = 0;
+      HIP_TRY(hipMalloc(&k->lidx, sizeof(int) * round_up(N, 1024)));
+      k->lidx_cap = round_up(N, 1024);
+    }
+    HIP_TRY(hipMemcpy(k->lidx, li.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    k->lidx_serial = m->serial;
+    k->lidx_valid = true;
+  }
+  if (k->off_row >= 0)
+    return set_err(MFGP_ERR_NO_LATTICE, "%s: training row %lld is not a cell of the grid's lattice", who,
+                   (long long)k->off_row);
+  return MFGP_OK;
+}
+
+int mfgp_sample_dims(mfgp_model* m, int64_t* dims, int n, int flags) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !dims)) return set_err(MFGP_ERR_ARG, "mfgp_sample_dims: null dims");
+  const bool prior = (flags & MFGP_SAMPLE_PRIOR) != 0;
+  if ((rc = sample_record(m, "mfgp_sample_dims"))) return rc;
+  if (!prior && (rc = sample_settle(m, "mfgp_sample_dims"))) return rc;
+  const mfgp_sample_rec* k = m->samp;
+  const int64_t v[8] = {sample_nz(m, prior), m->M, prior ? 0 : m->NL + m->NH, k->fields,
+                        k->rx[0], k->ry[0], k->rx[1], k->ry[1]};
+  for (int i = 0; i < n && i < 8; ++i) dims[i] = v[i];
+  return MFGP_OK;
+}
+
+int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64_t ldz, double* out, int64_t ldo,
+                          int flags) {
+  const char* who = "mfgp_sample_posterior";
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  mfgp_ctx* c = m->ctx;
+  const bool prior = (flags & MFGP_SAMPLE_PRIOR) != 0;
+  if (S < 0) return set_err(MFGP_ERR_ARG, "%s: negative sample count", who);
+  if (m->dtype == MFGP_F64 && m->M > 0 && ldo < m->M)
+    return set_err(MFGP_ERR_ARG, "%s: ldo = %lld is less than M = %lld", who, (long long)ldo, (long long)m->M);
+  if ((rc = sample_record(m, who))) return rc;
+  const mfgp_sample_rec* k = m->samp;
+  const int64_t N = prior ? 0 : m->NL + m->NH, M = m->M;
+  const int64_t nz = sample_nz(m, prior);
+  if (ldz < nz) return set_err(MFGP_ERR_ARG, "%s: ldz = %lld is less than nz = %lld", who, (long long)ldz, (long long)nz);
+  if (S > 0 && (!out || (nz > 0 && !normals))) return set_err(MFGP_ERR_ARG, "%s: null normals / output", who);
+  const bool z_dev = S > 0 && nz > 0 && is_device_ptr(normals);
+  const bool o_dev = S > 0 && is_device_ptr(out);
+  if (!z_dev && nz > 0)
+    for (int64_t s = 0; s < S; ++s)
+      if (!all_finite(normals + s * ldz, nz)) return set_err(MFGP_ERR_ARG, "%s: the normals must be finite", who);
+  const int64_t tw = std::max(std::max(k->ry[0], k->ry[1]), 1);
+  const size_t t_bytes = sizeof(double) * (size_t)SAMPLE_CHUNK * k->fields * k->nx * tw;
+  if (t_bytes > SAMPLE_T_MAX)
+    return set_err(MFGP_ERR_ARG, "%s: the axis factors' ranks (%d, %d) on %d x %d axes need more than %zu bytes of scratch",
+                   who, k->ry[0], k->ry[1], k->nx, k->ny, SAMPLE_T_MAX);
+  if (S == 0) return MFGP_OK;
+  if (N > 0) {
+    if ((rc = sample_settle(m, who))) return rc;
+    if ((rc = sample_lidx(m, who))) return rc;
+    if (m->ld > MAX_FULL_CAP + 64)
+      return set_err(MFGP_ERR_ARG, "%s supports a training capacity of at most %lld rows (this model's is %lld)", who,
+                     (long long)MAX_FULL_CAP, (long long)(m->ld - 1));
+  }
+  // workspace: [T | R | W | the chunk's normals (host normals) | the chunk's samples (host output)]
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const int64_t wld = std::max<int64_t>(prow_blocks(N) * PRB, PRB);
+  const size_t o_t = 0, o_r = o_t + up(t_bytes), o_w = o_r + up(sizeof(double) * wld * PBM);
+  const size_t o_z = o_w + up(sizeof(double) * wld * PBM);
+  const size_t o_o = o_z + (z_dev ? 0 : up(sizeof(double) * (size_t)SAMPLE_CHUNK * std::max<int64_t>(nz, 1)));
+  if ((rc = ensure_ws(c, o_o + (o_dev ? 0 : sizeof(double) * (size_t)SAMPLE_CHUNK * M)))) return rc;
+  char* ws = reinterpret_cast<char*>(c->ws);
+  const Hyp h = derive_hyp(m->kind, m->hyp, m->jitter);
+  const GridLattice& L = m->lat;
+  SampleArgs a{};
+  a.M = M;
+  a.fields = k->fields;
+  a.nx = L.nx;
+  a.ny = L.ny;
+  a.sx = L.sx;
+  a.sy = L.sy;
+  a.zoff[0] = 0;
+  a.zoff[1] = (int64_t)k->rx[0] * k->ry[0];
+  a.zoff[2] = a.zoff[1] + (int64_t)k->rx[1] * k->ry[1];
+  for (int f = 0; f < 2; ++f) {
+    a.rx[f] = k->rx[f];
+    a.ry[f] = k->ry[f];
+    a.Ax[f] = k->fac + k->off_ax[f];
+    a.AyT[f] = k->fac + k->off_ay[f];
+  }
+  a.T = reinterpret_cast<double*>(ws + o_t);
+  a.tw = tw;
+  a.cL = std::sqrt(h.sL);
+  a.cH[0] = m->kind == MFGP_SF ? std::sqrt(h.sL) : h.rho * std::sqrt(h.sL);
+  a.cH[1] = std::sqrt(h.sH);
+  a.mean = prior ? 0.0 : h.meanH;
+  a.meanL = h.meanL;
+  a.meanH = h.meanH;
+  a.sdL = std::sqrt(h.noiseL + h.jitter);
+  a.sdH = std::sqrt(h.noiseH + h.jitter);
+  a.y = m->y;
+  a.lidx = k->lidx;
+  a.N = N;
+  a.NL = m->NL;
+  a.R = reinterpret_cast<double*>(ws + o_r);
+  a.W = reinterpret_cast<double*>(ws + o_w);
+  a.wld = wld;
+  a.A = m->A;
+  a.Linv = m->Linv;
+  a.ld = m->ld;
+  a.V = reinterpret_cast<const double*>(m->V);
+  a.vld = m->vld;
+  for (int64_t s0 = 0; s0 < S; s0 += SAMPLE_CHUNK) {
+    const int64_t sc = std::min<int64_t>(SAMPLE_CHUNK, S - s0);
+    a.Sc = (int)sc;
+    if (z_dev || nz == 0) {
+      a.Z = normals ? normals + s0 * ldz : nullptr;
+      a.ldz = ldz;
+    } else {
+      double* dz = reinterpret_cast<double*>(ws + o_z);
+      HIP_TRY(hipMemcpy2DAsync(dz, sizeof(double) * nz, normals + s0 * ldz, sizeof(double) * ldz, sizeof(double) * nz,
+                               sc, hipMemcpyHostToDevice, c->stream));
+      a.Z = dz;
+      a.ldz = nz;
+    }
+    a.out = o_dev ? out + s0 * ldo : reinterpret_cast<double*>(ws + o_o);
+    a.ldo = o_dev ? ldo : M;
+    HIP_TRY(launch_sample_prior(a, c->stream));
+    if (N > 0) {
+      HIP_TRY(launch_sample_resid(a, c->stream));
+      HIP_TRY(launch_sample_solve(a, c->stream));
+      m->n_sample_solve += 1;
+      HIP_TRY(launch_sample_gemm(a, c->stream));
+      m->n_sample_gemm += 1;
+    }
+    if (!o_dev)
+      HIP_TRY(hipMemcpy2DAsync(out + s0 * ldo, sizeof(double) * ldo, a.out, sizeof(double) * M, sizeof(double) * M, sc,
+                               hipMemcpyDeviceToHost, c->stream));
+    if (!o_dev || !(z_dev || nz == 0)) HIP_TRY(hipStreamSynchronize(c->stream));   // the staging is reused by the next chunk
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MFGP_OK;
+}
+
 int mfgp_model_serial(const mfgp_model* m, uint64_t* serial) {
   if (!m || !serial) return set_err(MFGP_ERR_ARG, "null model/out");
   *serial = m->serial;
@@ -2468,11 +2814,11 @@ int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n) {
     if (m->kind == MFGP_MF) HIP_TRY(hipMemcpy(&nv[1], m->zvl + m->zb_rows + 1, sizeof(int), hipMemcpyDeviceToHost));
     virt = (int64_t)nv[0] + nv[1];
   }
-  const int64_t v[16] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
+  const int64_t v[18] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
                          m->n_full_predict, m->n_vstream, m->lat.nx, m->lat.ny, m->n_lattice, virt,
                          m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd,
-                         m->n_look_border, m->n_look_query};
-  for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
+                         m->n_look_border, m->n_look_query, m->n_sample_solve, m->n_sample_gemm};
+  for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
   return MFGP_OK;
 }
 int64_t mfgp_model_nl(const mfgp_model* m) { return m ? m->NL : -1; }

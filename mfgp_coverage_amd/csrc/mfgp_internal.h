@@ -290,6 +290,46 @@ struct LookArgs {
 };
 hipError_t launch_look_border(const LookArgs& a, hipStream_t s);
 hipError_t launch_look_query(const LookArgs& a, hipStream_t s);
+// pathwise samples on a lattice grid (mfgp_sample.hip): one chunk of Sc <= 64 samples.
+// The factor side (A, Linv, V, y for the N rows) is the model's; the axis factors, lidx
+// and the scratch (T, R, W) are the model's sample record and context workspace.
+constexpr int SAMPLE_CHUNK = 64;   // samples per set of launches (the solve's and the GEMM's columns)
+struct SampleArgs {
+  const double* Z;       // the chunk's normals [Sc][ldz]: field 0's rx0 x ry0 block, field 1's, then N
+  int64_t ldz;
+  int64_t zoff[3];       // offsets of the field blocks and of the noise block inside a sample's normals
+  double* out;           // [Sc][ldo], a sample's M cells contiguous
+  int64_t ldo, M;
+  int Sc, fields;        // samples of the chunk; 1 (SF) or 2 (MF: u_L, delta)
+  int nx, ny;
+  int64_t sx, sy;        // cell (ix, iy) = ix sx + iy sy
+  int rx[2], ry[2];      // ranks of the axis factors per field
+  const double* Ax[2];   // [nx][rx] row-major
+  const double* AyT[2];  // [ry][ny]: the y factor transposed
+  double* T;             // [Sc][fields][nx][tw]: Ax Z
+  int64_t tw;            // row width of T (>= ry)
+  double cH[2];          // hifi field = cH[0] u_0 + cH[1] u_1
+  double cL;             // a lofi row's field = cL u_0
+  double mean;           // added to the hifi field in out (m_H, or 0 for prior draws)
+  double meanL, meanH;   // prior means of lofi / hifi rows
+  double sdL, sdH;       // sqrt(noise + jitter) of lofi / hifi rows
+  const double* y;       // [N]
+  const int* lidx;       // [N] lattice indices px | (py << 16) of the training rows
+  int64_t N, NL;
+  double* R;             // [>= N][64] residuals (row, sample)
+  double* W;             // [wld][64]: L^-1 R
+  int64_t wld;           // rows of W (>= prow_blocks(N) * PRB)
+  const double* A;       // the factor, column-major [ld,ld]
+  const double* Linv;    // inverses of its diagonal blocks
+  int64_t ld;
+  const double* V;       // resident V [tiles][vld][64]
+  int64_t vld;
+};
+// k_sample_t + k_sample_field: out = mean + prior field
+hipError_t launch_sample_prior(const SampleArgs& a, hipStream_t s);
+hipError_t launch_sample_resid(const SampleArgs& a, hipStream_t s);
+hipError_t launch_sample_solve(const SampleArgs& a, hipStream_t s);
+hipError_t launch_sample_gemm(const SampleArgs& a, hipStream_t s);
 hipError_t launch_nlml_value(const GPDesc* d, int count, double* out, hipStream_t s);
 hipError_t launch_nlml_grad(const GPDesc* d, int64_t N, double* Xi, double* Kv, double* alpha, double* part,
                             hipStream_t s);

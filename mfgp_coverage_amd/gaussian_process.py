@@ -277,21 +277,70 @@ class _DeviceGP:
             return mu.reshape(-1, 1), DiagCov(var, fused)
         return mu.reshape(-1, 1), DiagCov(var, fused, source=m, serial=m.serial())
 
-    def draw_prior_samples(self, X_star, N_samples=1):
+    def _pathwise(self, X_star, N_samples, rng, normals, prior):
+        """Pathwise samples on the lattice grid X_star -> [M, N_samples] (_lib.Model.sample)."""
+        if not prior:
+            self._sync_data()
+        self._push_hyp()
+        self._grid_to_device(X_star)
+        m = self._dev()
+        try:
+            if normals is None:
+                nz = m.sample_dims(prior=prior)["nz"]
+                if rng is None:
+                    rng = np.random.default_rng()
+                draw = rng if callable(rng) else rng.standard_normal
+                normals = draw((int(N_samples), nz))
+            return m.sample(normals, prior=prior).T
+        except _lib.NoLatticeError as e:
+            raise ValueError(f"{e}; pathwise samples need a lattice grid with every training row on one of its "
+                             "cells: draw_posterior_samples / draw_prior_samples take the dense route") from None
+
+    def sample_posterior(self, X_star, N_samples=1, rng=None, normals=None):
+        """N_samples joint draws of predict(X_star)'s posterior on the whole grid ->
+        [M, N_samples], by pathwise (Matheron) conditioning from the resident V at a cost
+        linear in M (mfgp_sample_posterior): no M x M covariance is formed, so it
+        serves grids draw_posterior_samples cannot. X_star must be a lattice (meshgrid
+        order) and every training row one of its cells, else ValueError. rng: a
+        np.random.Generator (default np.random.default_rng()); normals [N_samples, nz]
+        (nz: _lib.Model.sample_dims) replaces the draw, and a sample's bits depend on its
+        own row of normals only."""
+        return self._pathwise(X_star, N_samples, rng, normals, False)
+
+    def sample_prior(self, X_star, N_samples=1, rng=None, normals=None):
+        """N_samples joint draws of the zero-mean (hifi) prior on the lattice grid X_star ->
+        [M, N_samples], from the separable axis factors (no data involved)."""
+        return self._pathwise(X_star, N_samples, rng, normals, True)
+
+    @staticmethod
+    def _method(method):
+        if method not in ("dense", "pathwise"):
+            raise ValueError("method must be 'dense' or 'pathwise'")
+        return method == "pathwise"
+
+    def draw_prior_samples(self, X_star, N_samples=1, method="dense"):
         """gaussian_process.py:180-191: N_samples joint draws of the zero-mean prior at
         X_star -> [n, N_samples]. K is the prior covariance k**(X_star, X_star) computed
         on the device (SF: s k; MF: the hifi prior rho^2 s_L k_L + s_H k_H); the draw is
-        numpy's (np.random.multivariate_normal, the global generator) as there."""
+        numpy's (np.random.multivariate_normal, the global generator) as there.
+        method="pathwise": sample_prior with normals from np.random.standard_normal (the
+        same global generator), linear in the grid's size."""
+        if self._method(method):
+            return self._pathwise(X_star, N_samples, np.random.standard_normal, None, True)
         self._push_hyp()
         self._grid_to_device(X_star)
         K = self._dev().cov_block(None, None, prior=True)
         return np.random.multivariate_normal(np.zeros(K.shape[0]), K, N_samples).T
 
-    def draw_posterior_samples(self, X_star, N_samples=1):
+    def draw_posterior_samples(self, X_star, N_samples=1, method="dense"):
         """gaussian_process.py:193-217: N_samples joint draws of the posterior at X_star ->
         [n, N_samples]. These are draws of predict(X_star)'s posterior (mean with the
         prior mean and centred observations, gp:132-143 / 414-432); the reference's
-        method leaves both out (gp:210-211), see DESIGN.md section 9."""
+        method leaves both out (gp:210-211), see DESIGN.md section 9.
+        method="pathwise": sample_posterior with normals from np.random.standard_normal
+        (the same global generator), without the dense covariance."""
+        if self._method(method):
+            return self._pathwise(X_star, N_samples, np.random.standard_normal, None, False)
         mu, cov = self.predict(X_star)
         return np.random.multivariate_normal(mu.flatten(), np.asarray(cov), N_samples).T
 
