@@ -212,6 +212,32 @@ int mfgp_view_max(const void* view, double* vmax, int64_t* argmax, int* valid);
 #define MFGP_COV_PRIOR 1
 int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
                    double* out, int64_t ldo, int flags);
+/* Integrated variance reduction per candidate cell (the A-optimal criterion): how
+ * much the weighted posterior variance of the whole grid falls if the hifi field is
+ * measured at grid cell cand[j],
+ *   out[k * ldo + j] = sum_i w[k * ldw + i] cov(i, cand[j])^2 / (cov(cand[j], cand[j]) + noise_H + jitter),
+ * i over all M cells (noise_H + jitter: the diagonal term a hifi append adds to K; an
+ * SF model's single noise), from the resident V (k_ivr_partial: k_cov_block's GEMM
+ * with the column sums of w o cov^2 reduced in registers, so the M x nc block never
+ * exists; k_ivr_finish: the division and the maxima). cand: a host array of grid cell
+ * indices in [0, M), any order, repeats allowed; NULL = all cells (then nc must equal
+ * M). w: nw <= MFGP_IVR_MAXW weight vectors [nw][ldw], ldw >= M, host or device
+ * memory; NULL = one vector of ones (then nw must be 1). Row tiles of 64 cells whose
+ * weights are zero in every vector are skipped, so a region mask costs its region.
+ * out: [nw][ldo], ldo >= nc, host or device memory. best / best_pos: host [nw], each
+ * optional: the maximum of out's row k and its first position in the candidate list.
+ * The call settles the model as mfgp_cov_block does (MFGP_ERR_NOT_PD, MFGP_ERR_NO_V as
+ * there) and validates everything before anything is enqueued: an index out of range,
+ * nw outside [1, MFGP_IVR_MAXW], ldw < M, ldo < nc, a non-finite weight in a host
+ * buffer, a model without a grid and an MFGP_F32 model return MFGP_ERR_ARG, launch
+ * nothing and leave the model as it was. nc == 0: MFGP_OK, nothing written. A model
+ * without training rows gives the prior's score (a grid, no factor needed). The model
+ * itself is not changed. out[k][j] depends bit for bit only on the model, the cell
+ * cand[j] and the weight vector k -- not on nc, j, the other candidates, nw or the
+ * other vectors -- and two calls agree bit for bit. */
+#define MFGP_IVR_MAXW 8
+int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
+                       double* out, int64_t ldo, double* best, int64_t* best_pos);
 /* The model's posterior serial: a value that changes whenever its training rows,
  * hyperparameters, jitter or grid change (appends, the batch entry points,
  * mfgp_truncate, mfgp_set_data / _set_hyp / _set_grid, the planners' loops), and is

@@ -19,6 +19,8 @@ OK, ERR_NOT_PD, ERR_ARG, ERR_DEVICE, ERR_NO_V, ERR_NO_LATTICE = 0, 1, 2, 3, 4, 5
 COV_PRIOR = 1
 SAMPLE_PRIOR = 1
 LOOK_MAX = 64   # prospective points per query (MFGP_LOOK_MAX)
+IVR_MAXW = 8    # weight vectors per var_reduction call (MFGP_IVR_MAXW)
+IVR_SEG_CELLS = 512   # grid cells per row segment of k_ivr_partial (8 tiles of 64): one partial sum each
 QueryResult = collections.namedtuple("QueryResult", ("mu", "var0", "var", "cov"))
 SF, MF = 0, 1
 F64, F32 = 0, 1
@@ -81,6 +83,9 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_int)]),
     "mfgp_cov_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "mfgp_var_reduction": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
     "mfgp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
@@ -426,6 +431,77 @@ class Model:
         buf = np.empty((na, nb), dtype=np.float64)
         check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(buf.ctypes.data), nb, flags))
         return buf
+
+    def var_reduction(self, cand=None, weights=None, out=None, with_best=False):
+        """Integrated variance reduction per candidate cell (mfgp_var_reduction): how much the
+        weighted posterior variance of the whole grid falls if the hifi field is measured at
+        cell cand[j], sum_i w_i cov(i, c)^2 / (cov(c, c) + noise_H + jitter), from the
+        resident V without the M x C block. cand: grid cell indices in [0, M) (any order,
+        repeats allowed), None = all cells. weights: None (ones), [M], or [nw, >= M] with
+        nw <= IVR_MAXW -- a float64 ndarray or a device tensor (anything with data_ptr(),
+        shape and stride()); a 2-D weights gives [nw, nc], else [nc]. out: a host float64
+        array or a device tensor of that shape to fill in place (a device out returns None
+        for the scores). with_best: (scores, best, best_pos) with the maximum of every row
+        and its first position in the candidate list (scalars for 1-D weights).
+        Settles the model as cov_block() does and leaves it unchanged; a score's bits depend
+        only on the model, its cell and its weight vector."""
+        L = lib()
+        M = L.mfgp_model_m(self.handle)
+        if cand is None:
+            cp, nc = None, M
+        else:
+            ca = np.ascontiguousarray(np.asarray(cand).reshape(-1), dtype=np.int64)
+            cp, nc = ctypes.c_void_p(ca.ctypes.data), ca.shape[0]
+
+        def dev2(t, what):   # a device tensor: (address, rows, columns, leading dimension, 2-D?)
+            shape, stride = tuple(t.shape), tuple(t.stride())
+            if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) not in (1, 2) or \
+                    (shape[-1] > 1 and stride[-1] != 1):
+                raise ValueError(f"{what} must be a float64 tensor [n] or [nw, n] with unit column stride")
+            two = len(shape) == 2
+            ld = int(stride[0]) if two and shape[0] > 1 else int(shape[-1])
+            return ctypes.c_void_p(int(t.data_ptr())), (int(shape[0]) if two else 1), int(shape[-1]), ld, two
+        if weights is None:
+            wp, nw, ldw, two = None, 1, M, False
+        elif hasattr(weights, "data_ptr"):
+            wp, nw, wn, ldw, two = dev2(weights, "weights")
+            if wn < M:
+                raise ValueError(f"weights must have at least M = {M} columns")
+        else:
+            wa = np.asarray(weights, dtype=np.float64)
+            if wa.ndim not in (1, 2) or wa.shape[-1] < M:
+                raise ValueError(f"weights must be [M] or [nw, >= M] with M = {M}")
+            two = wa.ndim == 2
+            wa = np.ascontiguousarray(wa.reshape(-1, wa.shape[-1]))
+            wp, nw, ldw = ctypes.c_void_p(wa.ctypes.data), wa.shape[0], wa.shape[1]
+        bv = np.empty(max(nw, 1), dtype=np.float64) if with_best else None
+        bp = np.empty(max(nw, 1), dtype=np.int64) if with_best else None
+
+        def op(a):
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+        if out is not None and hasattr(out, "data_ptr"):
+            o_p, orows, ocols, ldo, otwo = dev2(out, "out")
+            if otwo != two or orows < nw:
+                raise ValueError("out must have the shape of the result")
+            res = None
+        else:
+            if out is None:
+                buf = np.empty((nw, nc), dtype=np.float64)
+            else:
+                if not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != (2 if two else 1) or \
+                        out.strides[-1] != 8 or not out.flags.writeable or (two and (out.shape[0] < nw or
+                                                                                       out.strides[0] % 8)):
+                    raise ValueError("out must be a writable float64 array of the result's shape")
+                buf = out if two else out.reshape(1, -1)
+            ldo = int(buf.strides[0] // 8) if buf.shape[0] > 1 else int(buf.shape[1])
+            o_p = ctypes.c_void_p(buf.ctypes.data)
+            res = buf[:nw, :nc] if two else buf[0, :nc]
+        check(L.mfgp_var_reduction(self.handle, cp, nc, wp, nw, ldw, o_p, ldo, op(bv), op(bp)))
+        if not with_best:
+            return res
+        if two:
+            return res, bv[:nw], bp[:nw]
+        return res, np.float64(bv[0]), int(bp[0])
 
     def query(self, Xq, XL_new=None, XH_new=None, mu=True, var0=False, var=True, cov=False, ldc=None):
         """The posterior at arbitrary points Xq [n, 2], optionally with prospective lofi /

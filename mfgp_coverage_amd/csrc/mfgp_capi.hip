@@ -2311,6 +2311,105 @@ static bool all_finite(const double* p, int64_t n) {
   return true;
 }
 
+// Integrated variance reduction per candidate cell (mfgp_ivr.hip): k_cov_block's GEMM
+// over the resident V with the column sums of w o cov^2 kept in registers.
+int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
+                       double* out, int64_t ldo, double* best, int64_t* best_pos) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  mfgp_ctx* c = m->ctx;
+  const int64_t M = m->M;
+  if (m->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG,
+                   "mfgp_var_reduction: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
+  if (M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: the model has no grid (mfgp_set_grid)");
+  if (nc < 0) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: negative candidate count");
+  if (!cand && nc != M)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: a NULL candidate list means all %lld cells (got nc = %lld)",
+                   (long long)M, (long long)nc);
+  if (nw < 1 || nw > MFGP_IVR_MAXW)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: nw = %d is outside [1, %d]", nw, MFGP_IVR_MAXW);
+  if (!w && nw != 1)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: NULL weights mean one vector of ones (got nw = %d)", nw);
+  if (w && ldw < M)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: ldw = %lld is less than M = %lld", (long long)ldw, (long long)M);
+  if (ldo < nc)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: ldo = %lld is less than nc = %lld", (long long)ldo, (long long)nc);
+  if (ivr_segments(M) > 65535)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: grids of at most %lld cells are supported",
+                   (long long)65535 * IVR_SEG * PBM);
+  for (int64_t j = 0; cand && j < nc; ++j)
+    if (cand[j] < 0 || cand[j] >= M)
+      return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: cand[%lld] = %lld is outside the grid's cells [0, %lld)",
+                     (long long)j, (long long)cand[j], (long long)M);
+  const bool w_host = w && !is_device_ptr(w);
+  for (int k = 0; w_host && k < nw; ++k)
+    if (!all_finite(w + (int64_t)k * ldw, M))
+      return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: the weights must be finite (vector %d)", k);
+  if (nc == 0) return MFGP_OK;
+  if (!out) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: null output");
+  if (m->NL + m->NH > 0 && !v_covers(m)) {
+    // as mfgp_cov_block: the state mfgp_predict leaves, its result kept for the next predict
+    if ((rc = ensure_spec_out(m))) return rc;
+    m->spec_valid = false;
+    if ((rc = mfgp_predict(m, m->spec_out, m->spec_out + m->spec_cap))) return rc;
+    if (!v_covers(m))
+      return set_err(MFGP_ERR_NO_V,
+                     "mfgp_var_reduction: the resident V holds %lld of the model's %lld rows after a predict",
+                     (long long)m->v_n, (long long)(m->NL + m->NH));
+  }
+  // workspace: [cand | host weights [nw][M] | partial | out, when it is host memory | the
+  // workgroups' maxima and positions | best | best_pos], each 256-byte aligned
+  const bool o_host = !is_device_ptr(out);
+  const bool want_best = best || best_pos;
+  const int64_t nseg = ivr_segments(M), nblk = ivr_finish_blocks(nc);
+  size_t off = 0;
+  auto take = [&off](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  const size_t o_cand = take(cand ? sizeof(int64_t) * (size_t)nc : 0);
+  const size_t o_w = take(w_host ? sizeof(double) * (size_t)nw * M : 0);
+  const size_t o_part = take(sizeof(double) * (size_t)nseg * nw * nc);
+  const size_t o_out = take(o_host ? sizeof(double) * (size_t)nw * nc : 0);
+  const size_t o_bval = take(sizeof(double) * (size_t)nw * nblk);
+  const size_t o_bpos = take(sizeof(int64_t) * (size_t)nw * nblk);
+  const size_t o_best = take(sizeof(double) * MFGP_IVR_MAXW);
+  const size_t o_bp = take(sizeof(int64_t) * MFGP_IVR_MAXW);
+  if ((rc = ensure_ws(c, off))) return rc;
+  char* ws = reinterpret_cast<char*>(c->ws);
+  int64_t* dcand = cand ? reinterpret_cast<int64_t*>(ws + o_cand) : nullptr;
+  if (cand) HIP_TRY(hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, c->stream));
+  const double* dw = w;
+  int64_t dldw = ldw;
+  if (w_host) {
+    double* p = reinterpret_cast<double*>(ws + o_w);
+    HIP_TRY(hipMemcpy2DAsync(p, sizeof(double) * M, w, sizeof(double) * ldw, sizeof(double) * M, nw,
+                             hipMemcpyHostToDevice, c->stream));
+    dw = p;
+    dldw = M;
+  }
+  double* kout = o_host ? reinterpret_cast<double*>(ws + o_out) : out;
+  const int64_t kld = o_host ? nc : ldo;
+  double* dbest = want_best ? reinterpret_cast<double*>(ws + o_best) : nullptr;
+  int64_t* dbp = want_best ? reinterpret_cast<int64_t*>(ws + o_bp) : nullptr;
+  GPDesc d;
+  fill_desc(d, m);
+  HIP_TRY(launch_ivr(d, dcand, nc, dw, nw, dldw, reinterpret_cast<double*>(ws + o_part), kout, kld,
+                     reinterpret_cast<double*>(ws + o_bval), reinterpret_cast<int64_t*>(ws + o_bpos), dbest, dbp,
+                     c->stream));
+  if (o_host)
+    HIP_TRY(hipMemcpy2DAsync(out, sizeof(double) * ldo, kout, sizeof(double) * nc, sizeof(double) * nc, nw,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (best) HIP_TRY(hipMemcpyAsync(best, dbest, sizeof(double) * nw, hipMemcpyDeviceToHost, c->stream));
+  if (best_pos) HIP_TRY(hipMemcpyAsync(best_pos, dbp, sizeof(int64_t) * nw, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MFGP_OK;
+}
+
 int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq, const double* XL_new, int64_t nl_new,
                const double* XH_new, int64_t nh_new, double* mu, double* var0, double* var, double* cov,
                int64_t ldc) {

@@ -1,5 +1,5 @@
 // Device-side helpers shared by the HIP translation units of libmfgp_hip.so
-// (mfgp_kernels.hip, mfgp_nlml.hip, mfgp_cov.hip, mfgp_look.hip): f64 MFMA tile products,
+// (mfgp_kernels.hip, mfgp_nlml.hip, mfgp_cov.hip, mfgp_ivr.hip, mfgp_look.hip): f64 MFMA tile products,
 // LDS tile staging, the SE kernel in the reference's operation order
 // (gaussian_process.py:66-79), the K entries of gp:253-254 / gp:523-529, the 64x64
 // diagonal-block factor and inverse, and the steps of the left-looking forward
@@ -178,6 +178,15 @@ __device__ __forceinline__ void dma_rows64(double* dst, const double* __restrict
 }
 
 __device__ __forceinline__ void vm_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// (max, first position) of two candidates: the larger value, the lower index on ties
+// (np.argmax's rule)
+__device__ __forceinline__ void argmax_pair(double& bv, int64_t& bi, double ov, int64_t oi) {
+  if (ov > bv || (ov == bv && oi < bi)) {
+    bv = ov;
+    bi = oi;
+  }
+}
 
 // C/D element (mt, nt, v) of this lane <-> tile (row, col).
 __device__ __forceinline__ int acc_row(int wm, int mt, int q, int v) { return wm * 32 + mt * 16 + q + 4 * v; }

@@ -261,6 +261,20 @@ hipError_t launch_post_copy(const PostCopy* h, int count, hipStream_t s);
 // na / nb = M); prior_only: the k** term alone. Descriptor by value.
 hipError_t launch_cov_block(const GPDesc& d, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb,
                             double* out, int64_t ldo, int prior_only, hipStream_t s);
+// integrated variance reduction per candidate cell from the resident V (k_ivr_partial,
+// k_ivr_finish, k_ivr_best; mfgp_ivr.hip): out[k * ldo + j] = sum_i w[k * ldw + i]
+// cov(i, cand[j])^2 / (cov(cand[j], cand[j]) + noise_H + jitter), i over all d.M cells,
+// j < nc, k < nw <= IVR_MAXW. cand: a device list of cells in [0, M), or null = 0..M-1
+// (then nc = M); w: device weights, or null = one vector of ones (nw = 1). Scratch:
+// partial [ivr_segments(M)][nw][nc], bval / bpos [nw][ivr_finish_blocks(nc)]. best /
+// best_pos [nw] (device; both or neither): the max of out's row k and its first position.
+constexpr int IVR_MAXW = 8;   // weight vectors per call (= MFGP_IVR_MAXW)
+constexpr int IVR_SEG = 8;    // 64-cell row tiles per row segment (one partial sum each)
+inline int64_t ivr_segments(int64_t M) { return (ntiles_grid(M) + IVR_SEG - 1) / IVR_SEG; }
+inline int64_t ivr_finish_blocks(int64_t nc) { return (nc + NT - 1) / NT; }
+hipError_t launch_ivr(const GPDesc& d, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
+                      double* partial, double* out, int64_t ldo, double* bval, int64_t* bpos, double* best,
+                      int64_t* best_pos, hipStream_t s);
 // look-ahead variance and off-grid queries (k_look_border, k_look_query; mfgp_look.hip).
 // The factor side is the model's (A, Linv, zv for its N rows, current for h); the
 // record side (W, L22, L22inv, ppts, pfid, status) is the model's look-ahead record.

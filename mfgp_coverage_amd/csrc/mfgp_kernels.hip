@@ -361,12 +361,6 @@ __global__ __launch_bounds__(NT) void k_syrk_blk(const GPDesc* __restrict__ desc
 // is bumped; the last arriver reads the partials with agent-scope atomic loads
 // and resets the counter for the next launch. Called by wave 0 of the tile's
 // workgroup, lane l holding cell c0 + l (valid if inside the grid).
-__device__ __forceinline__ void argmax_pair(double& bv, int64_t& bi, double ov, int64_t oi) {
-  if (ov > bv || (ov == bv && oi < bi)) {
-    bv = ov;
-    bi = oi;
-  }
-}
 
 __device__ void var_argmax_tile(const GPDesc& d, double v, int64_t c, bool valid, int64_t tile) {
   const int lane = threadIdx.x & 63;

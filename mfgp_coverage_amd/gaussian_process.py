@@ -344,6 +344,22 @@ class _DeviceGP:
         mu, cov = self.predict(X_star)
         return np.random.multivariate_normal(mu.flatten(), np.asarray(cov), N_samples).T
 
+    def variance_reduction(self, X_star, candidates=None, weights=None):
+        """Integrated variance reduction per candidate: how much the weighted posterior
+        variance of predict(X_star), summed over all of X_star's points, falls if the
+        (hifi) field is measured at X_star[c], sum_i w_i cov(i, c)^2 / (cov(c, c) + noise +
+        jitter) -- the A-optimal criterion, from the resident V without the dense
+        covariance (_lib.Model.var_reduction). candidates: row indices
+        of X_star (any order, repeats allowed), None = every row. weights: None (ones),
+        [M] or [nw, M] with nw <= 8. Returns [nc], or [nw, nc] for 2-D weights. Not
+        available on precision="f32" models (TypeError, as their covariance blocks)."""
+        if self._dev().dtype != _lib.F64:
+            raise TypeError("variance_reduction needs the fp64 resident V: not available on precision='f32' models")
+        self._sync_data()
+        self._push_hyp()
+        self._grid_to_device(X_star)
+        return self._dev().var_reduction(candidates, weights)
+
     def _query(self, X, X_L_new=None, X_H_new=None, **want):
         """_lib.Model.query on the current data and hyperparameters (no grid involved)."""
         self._sync_data()
