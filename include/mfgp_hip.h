@@ -97,6 +97,18 @@ int mfgp_ctx_set_deferred_appends(mfgp_ctx* ctx, int enable);
  * it; 2 = take the lattice step for them too (tests). 0 = always the V stream
  * (k_inc_stream). Same numbers to rounding. */
 int mfgp_ctx_set_lattice(mfgp_ctx* ctx, int enable);
+/* The column store of V in the lattice step. A model in the lattice mode also keeps V
+ * by columns (Vc[cell][row], the memory of V again, within mfgp_ctx_set_vcol_budget):
+ * the step's producers and w units then read a new point's L21 row as contiguous
+ * bytes, and the w units start their pass over F at launch instead of after the
+ * producers' compact rows. mode -1 (default): a batch whose models all have a store
+ * takes it; 0: never, and no store is allocated; 1: as -1. Same bits either way.
+ * Also the environment variable MFGP_LAT_VCOL (0 / 1 / auto) at mfgp_ctx_create. */
+int mfgp_ctx_set_lattice_vcol(mfgp_ctx* ctx, int mode);
+/* Bytes one model's column store may take (-1: the built-in bound, 1 GiB, and a
+ * quarter of the free device memory; 0: no model gets a store). Models that have one
+ * keep it until their grid or row capacity changes. */
+int mfgp_ctx_set_vcol_budget(mfgp_ctx* ctx, int64_t bytes);
 /* Declare that this context's launches may run concurrently with launches of
  * other contexts on the same GPU (several streams stepping independent batches
  * side by side, e.g. a rank's seeds as four sub-batches). Default 0. With it no
@@ -341,8 +353,19 @@ int64_t mfgp_model_m(const mfgp_model* m);
  * appends of one GP that returned at the launch's published L22 verdict
  * (mfgp_append above), k_look_border launches and k_look_query launches of
  * mfgp_query (index 14 look_border, 15 look_query), k_sample_solve and k_sample_gemm
- * launches of mfgp_sample_posterior (index 16 sample_solve, 17 sample_gemm)}; n <= 18. */
+ * launches of mfgp_sample_posterior (index 16 sample_solve, 17 sample_gemm), lattice
+ * steps whose w units read the column store of V (index 18 lattice_vcol; a step with a
+ * new point off the lattice does not count), rows transposed into the store by its
+ * catch-up k_vcol_build (index 19 vcol_rows_built)}; n <= 20. */
 int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n);
+/* Tests only: the n = min(resident V rows, n_max) leading rows of V as doubles, v_out[i * M
+ * + c] = V(i, c), and of the column store, vc_out[c * n + i] (either may be null);
+ * *rows = n, *vc_rows = the store's valid rows (0: none). */
+int mfgp_debug_read_v(mfgp_model* m, double* v_out, double* vc_out, int64_t n_max, int64_t* rows,
+                      int64_t* vc_rows);
+/* Tests only: the explicit inverse F = L^-1 that the lattice steps keep, its n = min(current
+ * rows, n_max) leading rows and columns as doubles, f_out[i * n + j]; *rows = n (0: none). */
+int mfgp_debug_read_f(mfgp_model* m, double* f_out, int64_t n_max, int64_t* rows);
 /* Copy the lower Cholesky factor L [N,N] (row-major, zeros above the diagonal). */
 int mfgp_get_factor(mfgp_model* m, double* L_out);
 

@@ -42,6 +42,11 @@ SIGNATURES = {
     "mfgp_ctx_set_fused": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mfgp_ctx_set_deferred_appends": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mfgp_ctx_set_lattice": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "mfgp_ctx_set_lattice_vcol": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "mfgp_ctx_set_vcol_budget": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "mfgp_debug_read_v": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         _c_int64_p, _c_int64_p]),
+    "mfgp_debug_read_f": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_int64_p]),
     "mfgp_ctx_set_timing_stride": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "mfgp_ctx_set_concurrent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mfgp_batch_append_predict_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -222,6 +227,16 @@ class Context:
         GEMM tiles in the batch to fill the GPU), or always the one-pass V stream.
         on="force": also for batches too small to fill the GPU (tests)."""
         check(lib().mfgp_ctx_set_lattice(self.handle, 2 if on == "force" else (1 if on else 0)))
+
+    def set_lattice_vcol(self, mode="auto"):
+        """The lattice step's column store of V (mfgp_ctx_set_lattice_vcol): "auto" (default:
+        a batch whose models all have a store reads L21 from it), False (never, none is
+        allocated) or True (as auto). The results are the same bits either way."""
+        check(lib().mfgp_ctx_set_lattice_vcol(self.handle, -1 if mode == "auto" else (1 if mode else 0)))
+
+    def set_vcol_budget(self, nbytes=-1):
+        """Bytes one model's column store may take (-1: the built-in bound; 0: none)."""
+        check(lib().mfgp_ctx_set_vcol_budget(self.handle, int(nbytes)))
 
     def set_concurrent(self, on=True):
         """This context's launches may run beside other contexts' on the same GPU
@@ -610,13 +625,44 @@ class Model:
         because the model appended nothing (k_post_copy); {early_pd}: eager appends that
         returned at the launch's published L22 verdict (mfgp_append, one GP);
         {look_border, look_query}: the k_look_border / k_look_query launches of query();
-        {sample_solve, sample_gemm}: the k_sample_solve / k_sample_gemm launches of sample()."""
-        out = (ctypes.c_int64 * 18)()
-        check(lib().mfgp_model_stats(self.handle, out, 18))
+        {sample_solve, sample_gemm}: the k_sample_solve / k_sample_gemm launches of sample();
+        {lattice_vcol}: the lattice steps whose w units read the column store of V;
+        {vcol_rows_built}: the rows its catch-up (k_vcol_build) transposed into it."""
+        out = (ctypes.c_int64 * 20)()
+        check(lib().mfgp_model_stats(self.handle, out, 20))
         keys = ("factor_rows", "v_rows", "full_factor", "inc_factor", "full_predict", "vstream",
                 "lattice_nx", "lattice_ny", "lattice", "lattice_virtual", "lattice_arg", "lattice_g2",
-                "post_copy", "early_pd", "look_border", "look_query", "sample_solve", "sample_gemm")
+                "post_copy", "early_pd", "look_border", "look_query", "sample_solve", "sample_gemm",
+                "lattice_vcol", "vcol_rows_built")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def debug_read_v(self):
+        """Tests only: (V [n, M], Vc [M, n] or None, the store's valid rows): the resident V's
+        rows and the column store's, as float64."""
+        n, M = int(self.n), int(lib().mfgp_model_m(self.handle))
+        v = np.zeros((max(n, 1), max(M, 1)), dtype=np.float64)
+        vc = np.zeros((max(M, 1), max(n, 1)), dtype=np.float64)
+        rows, vcr = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().mfgp_debug_read_v(self.handle, ptr(v), None, n, ctypes.byref(rows), ctypes.byref(vcr)))
+        r = rows.value
+        vc = np.zeros((max(M, 1), max(r, 1)), dtype=np.float64)
+        check(lib().mfgp_debug_read_v(self.handle, None, ptr(vc), n, ctypes.byref(rows), ctypes.byref(vcr)))
+        return v[:r, :M], (vc[:M, :r] if vcr.value > 0 else None), int(vcr.value)
+
+    def debug_read_f(self):
+        """Tests only: the explicit inverse F = L^-1 the lattice steps keep, [n, n] float64
+        (n = 0: the model holds no current one)."""
+        n = int(self.n)
+        f = np.zeros((max(n, 1), max(n, 1)), dtype=np.float64)
+        rows = ctypes.c_int64(0)
+        check(lib().mfgp_debug_read_f(self.handle, ptr(f), n, ctypes.byref(rows)))
+        r = rows.value
+        if r == n:
+            return f[:n, :n]
+        g = np.zeros((max(r, 1), max(r, 1)), dtype=np.float64)
+        if r:
+            check(lib().mfgp_debug_read_f(self.handle, ptr(g), r, ctypes.byref(rows)))
+        return g[:r, :r]
 
     def sample_points(self, threshold, max_points):
         """compute_sample_points (simulator.py:326-374) on a device copy of this model:

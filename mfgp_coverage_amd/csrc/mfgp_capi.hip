@@ -130,6 +130,10 @@ struct mfgp_ctx {
   int lat_ksplit = 0;         // split-K of its GEMM tiles (0: chosen per launch; MFGP_LAT_KSPLIT, diagnostics)
   int lat_wu = 0;             // w units of a launch, all GPs (0: two per CU; MFGP_LAT_WU, diagnostics)
   int lat_selfg = -1;         // w units read L21 from V themselves (-1: for one GP; MFGP_LAT_SELFG, diagnostics)
+  int lat_vcol = -1;          // the producers and the w units read L21 from the column store of V (Vc): -1 for a
+                              // batch whose models all have one, 0 never (no store is allocated either), 1 the
+                              // same as -1 (a model without a store cannot take it); MFGP_LAT_VCOL, tests, A/B runs
+  int64_t vcol_budget = -1;   // bytes one model's store may take (-1: VCOL_MAX; 0: none; tests)
   int lat_gemm2 = -1;         // the step's GEMM and cells as a second launch (k_lat_gemm2): -1 where its
                               // tiles fill the chip once or twice, 1 always, 0 never (in-launch split-K
                               // tiles); MFGP_LAT_GEMM2, diagnostics and tests
@@ -236,6 +240,7 @@ struct mfgp_model {
   int64_t M = 0, Mcap = 0;
   double* grid = nullptr;
   GridLattice lat{};        // lattice structure of the grid (nx == 0: none)
+  std::vector<double> hax, hay;   // the lattice's axis values (host copy, for rows_on_cells)
   // resident V = L^-1 psi^T [vtiles][vld][PBM] (double, or float for MFGP_F32);
   // rows [0, v_n) valid for the current factor and grid
   void* V = nullptr;
@@ -316,6 +321,14 @@ struct mfgp_model {
   int64_t zflag_n = 0;
   unsigned* ldone = nullptr;  // [4] lattice phase hand-offs (arrivals | flag, twice)
   int* zvl = nullptr;         // [2][zb_rows + 1]
+  // the column store of V, Vc[cell][vc_ld] in V's element type: rows [0, vc_n) equal V's for
+  // generation vc_gen (allocated with the lattice state where the budget allows: ensure_vcol)
+  void* Vc = nullptr;
+  int64_t vc_ld = 0, vc_M = 0, vc_n = 0;
+  uint64_t vc_gen = 0;
+  int64_t vc_deny_ld = -1, vc_deny_M = -1, vc_deny_budget = -2;   // the shape and budget last refused
+  int64_t n_lattice_vcol = 0;  // lattice steps whose w units read the store
+  int64_t n_vcol_rows = 0;     // rows transposed into it by k_vcol_build (catch-up)
 };
 
 namespace {
@@ -670,6 +683,11 @@ void fill_desc(GPDesc& d, mfgp_model* m) {
   d.wpart = nullptr;
   d.wcnt = nullptr;
   d.lat_selfg = 0;
+  d.vcol = nullptr;
+  d.vcol_ld = 0;
+  d.vcol_lo = 0;
+  d.lat_vcol = 0;
+  d.pad_vcol = 0;
   d.lat_g2 = 0;
   d.lat_zcsr = 0;
   d.csr = nullptr;
@@ -899,6 +917,74 @@ int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu) {
   }
   return MFGP_OK;
 }
+// The column store of V for the model's grid and row capacity (vc_ld follows V's: a capacity
+// growth reallocates it and moves the valid rows to the new stride, as ensure_v moves V's, so
+// the step stays one that uploads nothing). It doubles V's memory, so it is bounded:
+// VCOL_MAX per model (the headline's 8 x 270 MB fit; configs[4]'s 2.1 GB per model do not, and
+// run as without a store) and a quarter of the free memory. A model that gets none runs the
+// step from the compact rows. The refusal is remembered per shape: no query per step.
+constexpr int64_t VCOL_MAX = int64_t(1) << 30;
+int ensure_vcol(mfgp_model* m) {
+  mfgp_ctx* c = m->ctx;
+  const int64_t ldc = m->vld, M = m->M;
+  if (m->Vc && m->vc_ld == ldc && m->vc_M == M) return MFGP_OK;
+  const int64_t budget = c->vcol_budget >= 0 ? c->vcol_budget : VCOL_MAX;
+  if (!m->Vc && m->vc_deny_ld == ldc && m->vc_deny_M == M && m->vc_deny_budget == budget) return MFGP_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // rows of the old store that stay valid at the new stride (the same grid and generation)
+  const int64_t keep =
+      (m->Vc && m->vc_gen == m->gen && m->vc_M == M) ? std::min({m->vc_n, m->v_n, ldc, m->vc_ld}) : 0;
+  void* const old = m->Vc;
+  const int64_t old_ld = m->vc_ld;
+  m->Vc = nullptr;
+  m->vc_n = 0;
+  m->vc_ld = m->vc_M = 0;
+  const size_t es = v_elem(m);
+  const int64_t bytes = (int64_t)es * M * ldc;
+  size_t free_b = 0, total_b = 0;
+  bool ok = c->lat_vcol != 0 && ldc > 0 && M > 0 && m->V && bytes <= budget;
+  if (ok && hipMemGetInfo(&free_b, &total_b) == hipSuccess) ok = (size_t)bytes <= free_b / 4;
+  if (ok && hipMalloc(&m->Vc, (size_t)bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    m->Vc = nullptr;
+    ok = false;
+  }
+  if (ok && old && keep > 0) {
+    HIP_TRY(hipMemcpy2DAsync(m->Vc, es * ldc, old, es * old_ld, es * keep, M, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m->vc_n = keep;
+  }
+  if (old) HIP_TRY(hipFree(old));
+  if (!ok) {
+    m->vc_deny_ld = ldc;
+    m->vc_deny_M = M;
+    m->vc_deny_budget = budget;
+    return MFGP_OK;
+  }
+  m->vc_ld = ldc;
+  m->vc_M = M;
+  return MFGP_OK;
+}
+// rows of the store that equal V's now
+int64_t vcol_rows(const mfgp_model* m) {
+  return (m->Vc && m->vc_gen == m->gen && m->vc_ld == m->vld && m->vc_M == m->M) ? std::min(m->vc_n, m->v_n) : 0;
+}
+// The kernels' uniform test (inc_gather_fast, lat_wblock) on the host, for the path counter:
+// is every new row the lattice cell its rounded axis estimate names? Rows the host does not
+// hold (device sources, staged rows) count as cells: the planners append grid cells.
+bool rows_on_cells(const mfgp_model* m, const GPDesc& d) {
+  const GridLattice& L = m->lat;
+  if (L.nx <= 0) return false;
+  if (!d.rows_inline || d.k_new != d.N - d.n0 || (int)m->hax.size() != L.nx || (int)m->hay.size() != L.ny) return true;
+  for (int64_t a = 0; a < d.k_new; ++a) {
+    const double px = d.rows_xy[2 * a], py = d.rows_xy[2 * a + 1];
+    if (!(px == px) || !(py == py)) return false;
+    const int ix = (int)std::rint(std::fmin(std::fmax((px - L.x0) * L.xinv, 0.0), (double)(L.nx - 1)));
+    const int iy = (int)std::rint(std::fmin(std::fmax((py - L.y0) * L.yinv, 0.0), (double)(L.ny - 1)));
+    if (!(m->hax[ix] == px && m->hay[iy] == py)) return false;
+  }
+  return true;
+}
 void free_lat(mfgp_model* m) {
   if (m->csr) (void)hipFree(m->csr);
   if (m->F) (void)hipFree(m->F);
@@ -917,6 +1003,7 @@ void free_lat(mfgp_model* m) {
   if (m->zflag) (void)hipFree(m->zflag);
   if (m->ldone) (void)hipFree(m->ldone);
   if (m->zvl) (void)hipFree(m->zvl);
+  if (m->Vc) (void)hipFree(m->Vc);
 }
 
 // Enqueue assembly + blocked Cholesky for `count` models (descriptors already uploaded).
@@ -1173,8 +1260,12 @@ int enqueue_inc_stream(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int coun
 // and the separable tables they need (k_trinv_f / k_lat_tables: only when a model
 // enters the mode with a new factor, grid or hyperparameters).
 int enqueue_inc_lat(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int count) {
-  int64_t max_blocks = 0, max_nbr = 0, max_rows = 0, max_axw = 0, max_tiles = 0;
+  int64_t max_blocks = 0, max_nbr = 0, max_rows = 0, max_axw = 0, max_tiles = 0, max_vcr = 0, max_vct = 0;
   for (int i = 0; i < count; ++i) {
+    if (hd[i].vcol && hd[i].vcol_lo < hd[i].n0) {
+      max_vcr = std::max(max_vcr, hd[i].n0 - hd[i].vcol_lo);
+      max_vct = std::max(max_vct, ntiles_grid(hd[i].M));
+    }
     max_blocks = std::max<int64_t>(max_blocks, hd[i].nprod + hd[i].nwu + hd[i].nzu + (hd[i].lat_zcsr ? 2 : 0) +
                                                    (hd[i].lat_g2 ? 0 : (int64_t)hd[i].lat_tiles * hd[i].ksplit));
     max_tiles = std::max<int64_t>(max_tiles, hd[i].lat_tiles);
@@ -1185,7 +1276,7 @@ int enqueue_inc_lat(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int count) 
   // the builds a new factor / grid / hyperparameters need, timed as factor work
   // (mfgp_ctx_get_timing's factor counters)
   EvPair evb{};
-  if (max_nbr > 0 || max_rows > 0 || max_axw > 0) {
+  if (max_nbr > 0 || max_rows > 0 || max_axw > 0 || max_vcr > 0) {
     int rc = ev_begin(c, evb, 1);
     if (rc) return rc;
   }
@@ -1220,6 +1311,8 @@ int enqueue_inc_lat(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int count) 
   }
   if (max_rows > 0) HIP_TRY(launch_lat_tables(dd, count, max_rows, c->stream));
   if (max_axw > 0) HIP_TRY(launch_lat_axes(dd, count, max_axw, c->stream));
+  // the column stores that are behind V (a new factor, V-stream steps since): caught up
+  if (max_vcr > 0) HIP_TRY(launch_vcol_build(dd, count, max_vcr, max_vct, hd[0].vf32, c->stream));
   {
     int rc = ev_end(c, evb);
     if (rc) return rc;
@@ -1239,7 +1332,8 @@ int enqueue_inc_lat(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int count) 
 bool desc_arg_ok(const mfgp_ctx* c, const GPDesc* hd, int count) {
   if (!c->desc_arg || count < 1 || count > DESC_ARG_MAX) return false;
   for (int i = 0; i < count; ++i)
-    if (hd[i].lat_fbuild || hd[i].n0 > hd[i].tab_lo || hd[i].lat_axbuild) return false;
+    if (hd[i].lat_fbuild || hd[i].n0 > hd[i].tab_lo || hd[i].lat_axbuild || (hd[i].vcol && hd[i].vcol_lo < hd[i].n0))
+      return false;
   return true;
 }
 
@@ -1551,6 +1645,10 @@ int mfgp_ctx_create(int device, mfgp_ctx** out) {
   if (const char* e = std::getenv("MFGP_LAT_KSPLIT")) c->lat_ksplit = std::max(0, std::min(8, std::atoi(e)));
   if (const char* e = std::getenv("MFGP_LAT_WU")) c->lat_wu = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("MFGP_LAT_SELFG")) c->lat_selfg = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MFGP_LAT_VCOL")) {
+    const int v = std::atoi(e);
+    c->lat_vcol = (e[0] == 'a' || v < 0) ? -1 : (v != 0 ? 1 : 0);
+  }
   if (const char* e = std::getenv("MFGP_LAT_GEMM2")) c->lat_gemm2 = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("MFGP_TRINV_COLUMNS")) c->trinv_columns = std::atoi(e) != 0;
   if (const char* e = std::getenv("MFGP_FACTOR_DEPTH")) c->factor_depth = std::max(1, std::min(16, std::atoi(e)));
@@ -1704,6 +1802,22 @@ int mfgp_ctx_set_lattice(mfgp_ctx* c, int enable) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->lattice = enable != 0;
   c->lat_force = enable == 2;
+  return MFGP_OK;
+}
+
+int mfgp_ctx_set_lattice_vcol(mfgp_ctx* c, int mode) {
+  if (!c) return set_err(MFGP_ERR_ARG, "null ctx");
+  if (const int rc_ = settle(c)) return rc_;   // (a running early-return launch first)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->lat_vcol = mode < 0 ? -1 : (mode != 0 ? 1 : 0);
+  return MFGP_OK;
+}
+
+int mfgp_ctx_set_vcol_budget(mfgp_ctx* c, int64_t bytes) {
+  if (!c) return set_err(MFGP_ERR_ARG, "null ctx");
+  if (const int rc_ = settle(c)) return rc_;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->vcol_budget = bytes < 0 ? -1 : bytes;
   return MFGP_OK;
 }
 
@@ -1872,6 +1986,8 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
     HIP_TRY(hipMemcpyAsync(m->grid, src->grid, sizeof(double) * 2 * src->M, hipMemcpyDeviceToDevice, c->stream));
     m->M = m->Mcap = src->M;
     m->lat = src->lat;
+    m->hax = src->hax;
+    m->hay = src->hay;
     // resident V (a deepcopy'd model keeps appending to the copy, sim:339)
     if (m->factored && src->V && src->v_n > 0 && src->vld == round_up(m->cap, PRB)) {
       if ((rc = ensure_v(m))) return rc;
@@ -1970,6 +2086,13 @@ int mfgp_set_grid(mfgp_model* m, const double* xs, int64_t M) {
     std::vector<double> h(2 * (size_t)M);
     HIP_TRY(hipMemcpy(h.data(), m->grid, sizeof(double) * 2 * M, hipMemcpyDeviceToHost));
     m->lat = detect_lattice(h.data(), M);
+    m->hax.assign((size_t)std::max(m->lat.nx, 0), 0.0);
+    m->hay.assign((size_t)std::max(m->lat.ny, 0), 0.0);
+    for (int i = 0; i < m->lat.nx; ++i) m->hax[i] = h[2 * (i * m->lat.sx)];
+    for (int i = 0; i < m->lat.ny; ++i) m->hay[i] = h[2 * (i * m->lat.sy) + 1];
+  } else {
+    m->hax.clear();
+    m->hay.clear();
   }
   return MFGP_OK;
 }
@@ -2037,6 +2160,7 @@ int mfgp_truncate(mfgp_model* m, int64_t n_keep_hifi) {
     if (m->factored && m->factor_N > N) m->factor_N = N;
     m->v_n = std::min(m->v_n, N);
     m->F_n = std::min(m->F_n, N);
+    m->vc_n = std::min(m->vc_n, N);
     m->tab_n = std::min(m->tab_n, N);
     for (int b = 0; b < 2; ++b)
       if (m->res_n[b] > N) m->res_n[b] = -1;   // the posterior of rows that are gone
@@ -2226,6 +2350,7 @@ int mfgp_predict(mfgp_model* m, double* mu, double* var) {
   if ((rc = upload_slot(c, slot, 1, &dd))) return rc;
   if ((rc = vst ? enqueue_vstream(c, dd, hd, 1) : enqueue_predict(c, dd, hd, 1))) return rc;
   (vst ? m->n_vstream : m->n_full_predict) += 1;
+  if (!vst) m->vc_n = 0;   // (a full predict rewrote V: the column store starts over)
   m->v_n = m->NL + m->NH;
   if (rb >= 0) res_tag(m, rb, m->v_n, 0);
   if ((rc = release_slot(c, slot))) return rc;
@@ -2913,11 +3038,71 @@ int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n) {
     if (m->kind == MFGP_MF) HIP_TRY(hipMemcpy(&nv[1], m->zvl + m->zb_rows + 1, sizeof(int), hipMemcpyDeviceToHost));
     virt = (int64_t)nv[0] + nv[1];
   }
-  const int64_t v[18] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
+  const int64_t v[20] = {m->factored ? m->factor_N : -1, m->v_n, m->n_full_factor, m->n_inc_factor,
                          m->n_full_predict, m->n_vstream, m->lat.nx, m->lat.ny, m->n_lattice, virt,
                          m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd,
-                         m->n_look_border, m->n_look_query, m->n_sample_solve, m->n_sample_gemm};
-  for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
+                         m->n_look_border, m->n_look_query, m->n_sample_solve, m->n_sample_gemm,
+                         m->n_lattice_vcol, m->n_vcol_rows};
+  for (int i = 0; i < n && i < 20; ++i) out[i] = v[i];
+  return MFGP_OK;
+}
+// Tests only: the resident V's n = min(v_n, n_max) leading rows as doubles, v_out[i * M + c] =
+// V(i, c), and the column store's, vc_out[c * n + i] (either may be null); *rows = n, *vc_rows
+// = the store's valid rows (0: none), both or neither.
+int mfgp_debug_read_v(mfgp_model* m, double* v_out, double* vc_out, int64_t n_max, int64_t* rows, int64_t* vc_rows) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  const int64_t n = m->V ? std::min(m->v_n, std::max<int64_t>(n_max, 0)) : 0, M = m->M;
+  const int64_t vcn = vcol_rows(m);
+  if (rows) *rows = n;
+  if (vc_rows) *vc_rows = vcn;
+  const size_t es = v_elem(m);
+  auto widen = [&](const std::vector<char>& raw, size_t e) {
+    return es == 8 ? reinterpret_cast<const double*>(raw.data())[e]
+                   : (double)reinterpret_cast<const float*>(raw.data())[e];
+  };
+  if (v_out && n > 0 && M > 0) {
+    std::vector<char> raw(es * (size_t)m->vtiles * m->vld * PBM);
+    HIP_TRY(hipMemcpy(raw.data(), m->V, raw.size(), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t c = 0; c < M; ++c) v_out[i * M + c] = widen(raw, (size_t)((c / PBM) * m->vld * PBM + i * PBM + c % PBM));
+  }
+  if (vc_out && n > 0 && M > 0 && m->Vc) {
+    std::vector<char> raw(es * (size_t)m->vc_M * m->vc_ld);
+    HIP_TRY(hipMemcpy(raw.data(), m->Vc, raw.size(), hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < M; ++c)
+      for (int64_t i = 0; i < n; ++i) vc_out[c * n + i] = widen(raw, (size_t)(c * m->vc_ld + i));
+  }
+  return MFGP_OK;
+}
+// Tests only: the explicit inverse F = L^-1 the lattice steps keep, rows and columns [0, n), n =
+// min(F's current rows, n_max), as doubles row-major f_out[i * n + j] (zeros above the diagonal);
+// *rows = n (0: the model holds no current F).
+int mfgp_debug_read_f(mfgp_model* m, double* f_out, int64_t n_max, int64_t* rows) {
+  const DeviceGuard dg_(m ? m->ctx->device : -1);
+  if (const int rc_ = settle(m ? m->ctx : nullptr)) return rc_;
+  int rc = check_model(m);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  const bool ff = m->dtype == MFGP_F32 && m->Ff;
+  const int64_t n = (m->F && m->F_gen == m->gen) ? std::min(m->F_n, std::max<int64_t>(n_max, 0)) : 0;
+  if (rows) *rows = n;
+  if (!f_out || n == 0) return MFGP_OK;
+  const int64_t ld = m->F_ld, tot = fblk_size(ld);
+  std::vector<double> h((size_t)tot);
+  if (ff) {
+    std::vector<float> hf((size_t)tot);
+    HIP_TRY(hipMemcpy(hf.data(), m->Ff, sizeof(float) * tot, hipMemcpyDeviceToHost));
+    for (int64_t e = 0; e < tot; ++e) h[e] = (double)hf[e];
+  } else {
+    HIP_TRY(hipMemcpy(h.data(), m->F, sizeof(double) * tot, hipMemcpyDeviceToHost));
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = 0; j < n; ++j)
+      f_out[i * n + j] = j <= i ? h[(size_t)(fblk_off(j / 64, ld) + (i - 64 * (j / 64)) * 64 + j % 64)] : 0.0;
   return MFGP_OK;
 }
 int64_t mfgp_model_nl(const mfgp_model* m) { return m ? m->NL : -1; }
@@ -3218,6 +3403,15 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
       // cache lines), which a batch's concurrent streams pay for (B = 8: 101.7 vs
       // 99.5 us) and one GP does not (57.1 vs 60.3 us)
       const int selfg = c->lat_selfg >= 0 ? c->lat_selfg : (ninc == 1 ? 1 : 0);
+      // the column store of V: taken by a batch whose models all have one (the w units
+      // then start F at launch; one GP prefers it to the V self-gather). A model that
+      // has a store keeps it written through whichever source the step reads
+      bool vcol_all = c->lat_vcol != 0;
+      for (int i = 0; i < ninc; ++i) {
+        mfgp_model* m = order[i];
+        if (c->lat_vcol != 0 && (rc = ensure_vcol(m))) return rc;
+        vcol_all = vcol_all && m->Vc != nullptr && m->vc_ld == m->vld && m->vc_M == m->M;
+      }
       for (int i = 0; i < ninc; ++i) {
         mfgp_model* m = order[i];
         GPDesc& fd = hd[i];
@@ -3262,6 +3456,13 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
         fd.zq = lat_zq(m);
         fd.lat_axbuild = m->axt_gen == m->gen ? 0 : 1;
         fd.lat_selfg = selfg;
+        if (c->lat_vcol != 0 && m->Vc && m->vc_ld == m->vld && m->vc_M == m->M) {
+          fd.vcol = m->Vc;
+          fd.vcol_ld = m->vc_ld;
+          // (the step's n0 rows of V are valid: fuse requires n0 == v_n)
+          fd.vcol_lo = std::min(vcol_rows(m), fd.n0);
+          fd.lat_vcol = vcol_all ? 1 : 0;
+        }
         fd.lat_g2 = g2 ? 1 : 0;
         // Z units reading the scan units' member lists (every lattice row count the scan
         // units bucket, rows and lattice indices within 16 bits)
@@ -3346,6 +3547,7 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
       mfgp_model* m = porder[i];
       m->v_n = m->NL + m->NH;
       (i < nv ? m->n_vstream : m->n_full_predict) += 1;
+      if (i >= nv) m->vc_n = 0;   // (a full predict rewrote V: the column store starts over)
       if (res_b[i] >= 0) res_tag(m, res_b[i], m->v_n, (lat && i < ninc) ? res_depth[i] : 0);
       if (lat && i < ninc) {
         m->n_lattice += 1;
@@ -3353,6 +3555,12 @@ static int batch_run(mfgp_model** models, int count, const double* X, const doub
         if (g2) m->n_lattice_g2 += 1;
         m->F_n = m->v_n;   // F's new rows and the new rows' tables came with the step
         m->F_gen = m->gen;
+        if (hd[i].vcol) {   // caught up to n0 ahead of the step, the new rows written through
+          m->n_vcol_rows += hd[i].n0 - hd[i].vcol_lo;
+          m->n_lattice_vcol += (hd[i].lat_vcol && rows_on_cells(m, hd[i])) ? 1 : 0;
+          m->vc_n = m->v_n;
+          m->vc_gen = m->gen;
+        }
         m->tab_n = m->v_n;
         m->tab_gen = m->gen;
         m->axt_gen = m->gen;
@@ -3383,12 +3591,13 @@ struct PlanSave {
   bool spec_valid, spec_max, pred_since_append;
   bool factored;
   int64_t factor_N, v_n;
-  int64_t cnt[9];
+  int64_t cnt[11];
 };
-static void plan_counters(const mfgp_model* m, int64_t (&v)[9]) {
-  const int64_t x[9] = {m->n_full_factor, m->n_inc_factor, m->n_full_predict, m->n_vstream, m->n_lattice,
-                        m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd};
-  for (int i = 0; i < 9; ++i) v[i] = x[i];
+static void plan_counters(const mfgp_model* m, int64_t (&v)[11]) {
+  const int64_t x[11] = {m->n_full_factor, m->n_inc_factor, m->n_full_predict, m->n_vstream, m->n_lattice,
+                         m->n_lattice_arg, m->n_lattice_g2, m->n_post_copy, m->n_early_pd,
+                         m->n_lattice_vcol, m->n_vcol_rows};
+  for (int i = 0; i < 11; ++i) v[i] = x[i];
 }
 // doubles of device room plan_enter needs for m's resident posterior
 static size_t plan_res_doubles(const mfgp_model* m) { return m->res ? 4 * (size_t)m->res_M : 0; }
@@ -3427,7 +3636,7 @@ static void plan_drop_async(mfgp_model* m) {
 static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   m->gate_dev = nullptr;
   plan_drop_async(m);
-  int64_t now[9];
+  int64_t now[11];
   plan_counters(m, now);
   int64_t* p = m->ctx->plan_stats;
   p[0] += 1;
@@ -3447,6 +3656,8 @@ static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   m->n_lattice_g2 = s.cnt[6];
   m->n_post_copy = s.cnt[7];
   m->n_early_pd = s.cnt[8];
+  m->n_lattice_vcol = s.cnt[9];
+  m->n_vcol_rows = s.cnt[10];
   m->NH = s.NH0;
   bump_serial(m);
   const int64_t N = m->NL + m->NH;
@@ -3463,6 +3674,7 @@ static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   m->factor_N = std::min(s.factor_N, N);
   m->v_n = std::max(std::min(m->v_n, N), std::min(s.v_n, N));
   m->F_n = std::min(m->F_n, N);
+  m->vc_n = std::min(m->vc_n, N);
   m->tab_n = std::min(m->tab_n, N);
   m->l21c_N = -1;   // (the compact rows in iscr are the loop's now)
   if (failed) {

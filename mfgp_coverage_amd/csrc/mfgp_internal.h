@@ -146,6 +146,14 @@ struct GPDesc {
                        // lattice row in csr, and the Z units read their rows' lists (lat_zunit_csr)
   unsigned* csr;       // member lists, per part [tabw + 1 + ld]: offsets by lattice y-row [ny + 1],
                        // then the members (px << 16) | j in row order, rows ascending (csr_bytes)
+  // the column store of V (lattice mode): Vc[c * vcol_ld + i] == V(i, c) in V's element type, the
+  // rows of one cell contiguous (V itself keeps a cell's rows PBM elements apart)
+  void* vcol;          // null: the model has none (then nothing below is read)
+  int64_t vcol_ld;     // elements per column (V's row capacity)
+  int64_t vcol_lo;     // k_vcol_build: rows [vcol_lo, n0) are transposed from V ahead of the step
+  int lat_vcol;        // 1 = the store holds rows [0, n0) at the step: the producers and the w units
+                       // read L21 from its columns (the w units without waiting for the producers)
+  int pad_vcol;
   Hyp hf;              // hyperparameters of the factorisation (updt_info time)
   Hyp hp;              // hyperparameters of predict (predict time)
 };
@@ -223,6 +231,10 @@ hipError_t launch_inc_lat_arg(const GPDesc* h, int count, int64_t max_blocks, in
                               hipStream_t s);
 // separable tables and lattice indices of rows [tab_lo, n0); max_rows = max over GPs of n0 - tab_lo
 hipError_t launch_lat_tables(const GPDesc* d, int count, int64_t max_rows, hipStream_t s);
+// the column store's catch-up (k_vcol_build): rows [vcol_lo, n0) of V into Vc for the GPs whose store
+// is behind; max_rows = max over GPs of n0 - vcol_lo, max_tiles = max over GPs of ntiles_grid(M)
+hipError_t launch_vcol_build(const GPDesc* d, int count, int64_t max_rows, int64_t max_tiles, int vf32,
+                             hipStream_t s);
 // axis tables (GPs with lat_axbuild); max_tabw = max over GPs of tabw
 hipError_t launch_lat_axes(const GPDesc* d, int count, int64_t max_tabw, hipStream_t s);
 // F = L^-1 of the n0 factor rows (block column per workgroup); max_nbr = max nblocks_rows(n0)

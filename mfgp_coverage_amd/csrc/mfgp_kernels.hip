@@ -790,6 +790,36 @@ __device__ __forceinline__ const VT* vres_ptr(const GPDesc& d) {
   if constexpr (sizeof(VT) == 8) return d.V;
   else return d.Vf;
 }
+// The column store of V (GPDesc::vcol) in the precision VT, or null.
+template <class VT>
+__device__ __forceinline__ const VT* vcol_ptr(const GPDesc& d) {
+  return static_cast<const VT*>(d.vcol);
+}
+// The new rows [n0, n0 + k) of cell c into the column store: 8 k (fp32: 4 k) contiguous bytes,
+// in 16-byte stores where n0 leaves them aligned (vcol_ld is a multiple of PRB); write-through
+// (k_lat_gemm2's cells leave no dirty lines, as their other stores).
+template <int KA, class VT>
+__device__ __forceinline__ void vcol_store(const GPDesc& d, int64_t c, int64_t n0, int k, const double (&vn)[KA]) {
+  VT* const p = const_cast<VT*>(vcol_ptr<VT>(d)) + c * d.vcol_ld + n0;
+  constexpr int W = 16 / (int)sizeof(VT);   // elements per 16-byte store
+  const bool al = (n0 & (W - 1)) == 0;
+#pragma unroll
+  for (int a = 0; a < KA; a += W) {
+    if (al && a + W <= k) {
+      if constexpr (sizeof(VT) == 8) {
+        const dv2 v{vn[a], vn[a + 1]};
+        st16_wt(p + a, v);
+      } else {
+        const f4 v{(float)vn[a], (float)vn[a + 1], (float)vn[a + 2], (float)vn[a + 3]};
+        st16_wt(reinterpret_cast<double*>(p + a), __builtin_bit_cast(dv2, v));
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < W; ++b)
+        if (a + b < k) __hip_atomic_store(p + a + b, (VT)vn[a + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
 
 // Partial L21 L21^T and L21 z1 over rows [j_lo, j_hi) into red[w][ISZ] (one slot per
 // wave). Lane (r, q) holds L21[r][j], j = 4s + q, eight 4-row steps in flight per
@@ -947,13 +977,17 @@ __device__ __forceinline__ bool inc_gather_fast(const GPDesc& d, int64_t j_lo, i
   const int iy = (int)rint(fmin(fmax((py - L.y0) * L.yinv, 0.0), (double)(L.ny - 1)));
   const int64_t cr = (px == px && py == py) ? ix * L.sx + iy * L.sy : 0;
   const dv2 g = reinterpret_cast<const GLOBAL dv2*>(gp(d.grid))[cr];
-  const VT* src = vres_ptr<VT>(d) + (cr / PBM) * d.vld * PBM + (cr % PBM);
+  // the cell's column: contiguous in the column store when it holds the n0 rows, else
+  // PBM elements apart in V (a 128-byte line per row)
+  const bool vc = d.lat_vcol != 0;
+  const VT* src = vc ? vcol_ptr<VT>(d) + cr * d.vcol_ld : vres_ptr<VT>(d) + (cr / PBM) * d.vld * PBM + (cr % PBM);
+  const int64_t sstr = vc ? 1 : PBM;
   double a[IU], zz[IU];
 #pragma unroll
   for (int u = 0; u < IU; ++u) {
     const int64_t j = j_lo + 4 * (w + NW * u) + q;
     const int64_t jj = j < j_hi ? j : j_lo;
-    a[u] = (double)gp(src)[jj * PBM];
+    a[u] = (double)gp(src)[jj * sstr];
     zz[u] = gp(zv)[jj];
   }
   const bool miss = r < k && !(g.x == px && g.y == py);

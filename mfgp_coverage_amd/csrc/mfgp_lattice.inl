@@ -398,16 +398,21 @@ __device__ __forceinline__ void lat_wblock(const GPDesc& d, int64_t u, double* s
       const dv2 g = reinterpret_cast<const GLOBAL dv2*>(gp(d.grid))[cr[t]];
       miss = miss || (a < k && !(g.x == px && g.y == py));
     }
-    selfg = d.lat_selfg && L.nx > 0 && d.vres >= n0 && vres_ptr<VT>(d) != nullptr && __ballot(miss) == 0;
+    const bool oncell = L.nx > 0 && __ballot(miss) == 0;
+    // the column store first (it holds the n0 rows: lat_vcol): a 16-row step's A operand is
+    // then 128 contiguous bytes per new point, where V's own layout costs a line per row
+    const bool vcg = d.lat_vcol && oncell;
+    selfg = vcg || (d.lat_selfg && oncell && d.vres >= n0 && vres_ptr<VT>(d) != nullptr);
     // (lanes whose row a >= k carry no point: they read row 0's element, the same
     // line, so the compact rows' unused part costs no traffic; their MFMA input is zeroed)
 #pragma unroll
     for (int t = 0; t < NA; ++t) {
       const int a = ar0 + 4 * t;
-      asrc[t] = selfg ? vres_ptr<VT>(d) + (cr[t] / PBM) * d.vld * PBM + (cr[t] % PBM)
+      asrc[t] = vcg     ? vcol_ptr<VT>(d) + cr[t] * d.vcol_ld
+                : selfg ? vres_ptr<VT>(d) + (cr[t] / PBM) * d.vld * PBM + (cr[t] % PBM)
                       : reinterpret_cast<const VT*>(l21c) + (a < k ? a : 0);
     }
-    astr = selfg ? (int64_t)PBM : (int64_t)KINC;
+    astr = vcg ? (int64_t)1 : (selfg ? (int64_t)PBM : (int64_t)KINC);
   }
   auto load_a = [&](const Cur& c, ARow& a) {
     const int64_t i = row_of(c);
@@ -1548,7 +1553,8 @@ __device__ __forceinline__ void lat_epi(const GPDesc& d, int64_t tile, int64_t s
   double bv = -__builtin_inf();
   int64_t bi = INT64_MAX;
   VT* const Vr = const_cast<VT*>(vres_ptr<VT>(d));
-  const int64_t vld = d.vld;
+  VT* const Vcb = const_cast<VT*>(vcol_ptr<VT>(d));   // the column store (or null)
+  const int64_t vld = d.vld, vcld = d.vcol_ld;
   double* const omu = d.mu;
   double* const ovar = d.var;
   double* const rmu = d.rmu;
@@ -1569,6 +1575,7 @@ __device__ __forceinline__ void lat_epi(const GPDesc& d, int64_t tile, int64_t s
     const int ixc = (int)(ix - ix0), iyc = IXPT + (int)(iy - iy0);
     const double* const Tc = Ts + (cw * 16 + (KA == 8 ? 8 * ch : 0)) * TW + cyl;
     VT* const vt = Vr + (c / PBM) * vld * PBM + (c % PBM);
+    VT* const vcp = Vcb ? Vcb + c * vcld + n0 : nullptr;
     double vn[KA];
     double vs = 0.0, ms = 0.0;
 #pragma unroll
@@ -1585,6 +1592,7 @@ __device__ __forceinline__ void lat_epi(const GPDesc& d, int64_t tile, int64_t s
         vs += vn[a] * vn[a];
         ms += vn[a] * L22[KINC * KINC + a];
         vt[(n0 + a) * PBM] = (VT)vn[a];
+        if (vcp) vcp[a] = (VT)vn[a];   // (the cell's new rows: contiguous)
       }
     }
     const double vc = cov - vs;
@@ -2163,6 +2171,50 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
       __hip_atomic_store(d.rvar + c, vc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
+  // The cells' new rows into the column store: a cell's KA values are contiguous there, but the
+  // cells of a wave lie a column apart, so a store per thread is 64 requests of 16 bytes per
+  // instruction (measured: this launch 24.0 -> 31.0 us at the headline). The wave's 64 x KA values
+  // go through LDS instead -- its own rows of split 0's sums, which only its cells read, above --
+  // and come back with the 16-byte chunks of one cell on neighbouring lanes: whole 64-byte (KA 16:
+  // 128-byte) runs per request. Rows that n0 leaves unaligned take the per-thread form.
+  auto store_vcol = [&]() {
+    if (!d.vcol || wg >= IXPT) return;   // (wave-uniform: the waves that own cells)
+    constexpr int W = 16 / (int)sizeof(VT);   // elements of a 16-byte chunk
+    constexpr int NCH = KA / W;               // chunks per cell
+    constexpr int CPI = 64 / NCH;             // cells per store instruction
+    if ((n0 & (W - 1)) != 0) {
+      if (c >= 0) vcol_store<KA, VT>(d, c, n0, k, vn);
+      return;
+    }
+    VT* const Pw = reinterpret_cast<VT*>(sm + wg * KA * 64);
+    __builtin_amdgcn_wave_barrier();   // (the wave's reads of these rows are issued: LDS runs in order)
+#pragma unroll
+    for (int a = 0; a < KA; ++a) Pw[lane * KA + a] = (VT)(c >= 0 ? vn[a] : 0.0);
+    __builtin_amdgcn_wave_barrier();
+    const int ch = lane % NCH, sub = lane / NCH;
+    const int64_t ix = ix0 + wg;
+    VT* const vcb = const_cast<VT*>(vcol_ptr<VT>(d));
+    const int64_t ldc = d.vcol_ld;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int cc = CPI * j + sub;
+      const int64_t iy = iy0 + cc;
+      const dv2 v = *reinterpret_cast<const dv2*>(Pw + cc * KA + ch * W);
+      if (ix < lat.nx && iy < lat.ny && ch * W < k) {
+        VT* const p = vcb + (ix * lat.sx + iy * lat.sy) * ldc + n0 + ch * W;
+        if (ch * W + W <= k) {
+          st16_wt(reinterpret_cast<double*>(p), v);
+        } else {
+          VT e[W];
+          __builtin_memcpy(e, &v, 16);
+#pragma unroll
+          for (int b = 0; b < W; ++b)
+            if (ch * W + b < k) __hip_atomic_store(p + b, e[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+  };
+  store_vcol();
   if (d.vmax || d.vargmax || d.status_host) {
     // The tile counts in (var_argmax_group: a store, a returning add and, on the GP's
     // last tile, a load and a store, each waiting for the one before) ahead of the
@@ -2241,6 +2293,40 @@ __global__ __launch_bounds__(NT) void k_lat_axes(const GPDesc* __restrict__ desc
     const int64_t p = rr % (tabw + 1);
     d.axt[rr * tabw + col] = p < tabw ? lat_axis_value(d, t, p, col) : 0.0;
   }
+}
+
+// The column store's catch-up: rows [vcol_lo, n0) of V transposed into Vc, one 64-row x
+// 64-cell block per workgroup through LDS (V: a row's 64 cells contiguous; Vc: a cell's
+// rows contiguous). Grid (row blocks from vcol_lo, 64-cell tiles, GPs). The index map is
+// restated in tests/test_vcol_host.py.
+template <class VT>
+__global__ __launch_bounds__(NT) void k_vcol_build(const GPDesc* __restrict__ descs) {
+  const GPDesc& d = descs[blockIdx.z];
+  VT* const vc = const_cast<VT*>(vcol_ptr<VT>(d));
+  const VT* const v = vres_ptr<VT>(d);
+  if (!vc || !v) return;
+  const int64_t hi = d.n0, M = d.M, vld = d.vld, ldc = d.vcol_ld;
+  const int64_t r0 = d.vcol_lo + 64 * (int64_t)blockIdx.x, tile = blockIdx.y;
+  if (r0 >= hi || tile * PBM >= M) return;
+  __shared__ VT blk[64][65];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const VT* const vt = v + tile * vld * PBM;
+  for (int rr = w; rr < 64; rr += NT / 64)
+    if (r0 + rr < hi) blk[rr][lane] = vt[(r0 + rr) * PBM + lane];
+  __syncthreads();
+  for (int cc = w; cc < 64; cc += NT / 64) {
+    const int64_t c = tile * PBM + cc;
+    if (c < M && r0 + lane < hi) vc[c * ldc + r0 + lane] = blk[lane][cc];
+  }
+}
+
+hipError_t launch_vcol_build(const GPDesc* d, int count, int64_t max_rows, int64_t max_tiles, int vf32,
+                             hipStream_t s) {
+  if (count < 1 || max_rows <= 0 || max_tiles <= 0) return hipSuccess;
+  const dim3 g((unsigned)((max_rows + 63) / 64), (unsigned)max_tiles, (unsigned)count);
+  if (vf32) hipLaunchKernelGGL(k_vcol_build<float>, g, dim3(NT), 0, s, d);
+  else hipLaunchKernelGGL(k_vcol_build<double>, g, dim3(NT), 0, s, d);
+  return hipGetLastError();
 }
 
 // MFGP_F32: Ff = (float) F over F's storage, for the GPs whose F was just built
