@@ -1,0 +1,467 @@
+// What the host translation units of libmfgp_hip.so share (host only; no kernel file
+// includes it): error reporting, the device guard, the constants, the context and
+// model state behind the C ABI's opaque handles, and the helpers that cross files.
+//
+//   mfgp_capi.hip      contexts, models, their state helpers, set / append / predict, stats
+//   mfgp_step.hip      the step engine: enqueue_*, batch_run, the batch entry points
+//   mfgp_planners.hip  the sample-point loops and the cell reductions
+//   mfgp_resident.hip  consumers of the resident V and factor: covariance blocks,
+//                      variance reduction, look-ahead queries, pathwise samples
+//   mfgp_train.hip     NLML and its gradient, single and batched
+//
+// The shared helpers live in mfgp_host, a namespace of hidden visibility: they link
+// across the library's objects and add nothing to its dynamic symbol table.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/mfgp_hip.h"
+#include "mfgp_internal.h"
+
+namespace mfgp_host __attribute__((visibility("hidden"))) {
+
+// the thread's error string (mfgp_last_error); returns code
+int set_err(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess) return mfgp_host::set_err(MFGP_ERR_DEVICE, "%s: %s (%s:%d)", #expr, \
+                                                    hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+// The context's device for the duration of one entry point, the caller's restored on
+// every return path (an entry point that set the device and left it
+// changed torch.cuda.current_device() in a multi-GPU process). dev < 0: no change.
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (dev < 0 || hipGetDevice(&prev) != hipSuccess) {
+      prev = -1;
+      return;
+    }
+    if (prev == dev || hipSetDevice(dev) != hipSuccess) prev = -1;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+constexpr int RING = 64;       // descriptor upload slots
+constexpr int MAXB = 256;      // GPs per launch
+constexpr int64_t MAX_FULL_CAP = 16319;   // largest training capacity the full predict serves (ld <= 16383)
+constexpr size_t F32_SCRATCH = size_t(16) << 30;   // bytes of fp64 V scratch for MFGP_F32 full predicts
+// bytes of scratch a chunk of mfgp_nlml_batch may hold (a member: its factor A, and Xi
+// and Kv with the gradient, ld^2 doubles each): 40 members with the gradient at N = 2048
+constexpr size_t NLML_BATCH_SCRATCH = size_t(4) << 30;
+// lattice-separable step (k_inc_lat): taken when kss / (smallest noise + jitter)
+// <= LAT_RMAX (its error grows with the conditioning of K),
+// and for at most LAT_MAXD consecutive steps before var / mu are recomputed from V
+constexpr double LAT_RMAX = 1e4;
+constexpr int LAT_MAXD = 256;
+// planner counters (mfgp_ctx_planner_stats): model runs, bordered appends, V-stream
+// predicts, lattice steps (of them by value / with k_lat_gemm2), full factors, full
+// predicts; then the batched planner's host time (us) before, in and after its loop
+constexpr int PLAN_NSTATS = 11;
+
+constexpr int STATUS_UNSET = INT_MIN + 1;   // status_host before the launch writes it
+
+struct EvPair {
+  hipEvent_t a, b;
+  int kind;  // 0 predict, 1 factor
+};
+
+// The path counters of a model (mfgp_model::cnt). mfgp_model_stats reports them; a
+// planner's loop saves and restores the whole array (PlanSave) and moves its steps to
+// the context's planner counters by name, so a new counter is added here alone.
+enum PathCounter {
+  N_FULL_FACTOR,
+  N_INC_FACTOR,
+  N_FULL_PREDICT,
+  N_VSTREAM,
+  N_LATTICE,
+  N_LATTICE_ARG,    // lattice steps launched with their descriptors by value (k_inc_lat_arg)
+  N_LATTICE_G2,     // lattice steps whose GEMM and cells ran as a second launch (k_lat_gemm2)
+  N_POST_COPY,      // batch predicts served from the resident posterior (k_post_copy: nothing appended)
+  N_EARLY_PD,       // eager appends that returned at the launch's published L22 verdict
+  N_LATTICE_VCOL,   // lattice steps whose w units read the store
+  N_VCOL_ROWS,      // rows transposed into it by k_vcol_build (catch-up)
+  N_LOOK_BORDER,    // k_look_border / k_look_query launches
+  N_LOOK_QUERY,
+  N_SAMPLE_SOLVE,   // k_sample_solve / k_sample_gemm launches
+  N_SAMPLE_GEMM,
+  N_COUNTERS
+};
+
+}  // namespace mfgp_host
+
+struct mfgp_ctx {
+  int device = 0;
+  hipStream_t own = nullptr;
+  hipStream_t stream = nullptr;
+  // descriptor ring
+  mfgp::GPDesc* h_ring = nullptr;  // pinned [RING][MAXB]
+  mfgp::GPDesc* d_ring = nullptr;  // device [RING][MAXB]
+  hipEvent_t ring_ev[mfgp_host::RING];
+  bool ring_used[mfgp_host::RING];
+  int ring_pos = 0;
+  // workspace (V scratch + device outputs for host-pointer calls)
+  double* ws = nullptr;
+  size_t ws_bytes = 0;
+  // timing: 0 off, 1 predict + factor launches, 2 predict launches only
+  int timing = 0;
+  int64_t timing_stride = 1, timing_seq = 0;   // bracket every stride-th eligible launch
+  std::vector<mfgp_host::EvPair> pending;
+  std::vector<hipEvent_t> pool;
+  double t_predict = 0.0, t_factor = 0.0;
+  int64_t n_predict = 0, n_factor = 0;
+  // deferred status words of ASYNC batches, with the model each belongs to (a
+  // failed factor is dropped from its model at mfgp_ctx_synchronize)
+  struct AsyncStatus {
+    mfgp_model* m;
+    int* dev;      // the model's status word (device)
+    int* host;     // its mapped host copy written by the launch (k_inc_stream1), or null: copy dev
+  };
+  std::vector<AsyncStatus> async_status;
+  // fp64 scratch in which the full predicts of MFGP_F32 models compute V
+  // (k_predict re-reads its own rows), then rounded into their fp32 V
+  double* vscr = nullptr;
+  size_t vscr_bytes = 0;
+  int f32_group = 1;          // full predicts per k_predict launch that share vscr
+  // incremental append / predict (bordered Cholesky + resident V); off = always
+  // refactor and recompute V from scratch, as the reference does
+  bool incremental = true;
+  bool fused = true;          // bordered append + one-pass predict in one launch (k_inc_stream)
+  bool deferred = false;      // mfgp_append stages rows for a later (fused) bordered append
+  bool lattice = true;        // lattice-separable appends (k_inc_lat) where they apply
+  int lat_ksplit = 0;         // split-K of its GEMM tiles (0: chosen per launch; MFGP_LAT_KSPLIT, diagnostics)
+  int lat_wu = 0;             // w units of a launch, all GPs (0: two per CU; MFGP_LAT_WU, diagnostics)
+  int lat_selfg = -1;         // w units read L21 from V themselves (-1: for one GP; MFGP_LAT_SELFG, diagnostics)
+  int lat_vcol = -1;          // the producers and the w units read L21 from the column store of V (Vc): -1 for a
+                              // batch whose models all have one, 0 never (no store is allocated either), 1 the
+                              // same as -1 (a model without a store cannot take it); MFGP_LAT_VCOL, tests, A/B runs
+  int64_t vcol_budget = -1;   // bytes one model's store may take (-1: VCOL_MAX; 0: none; tests)
+  int lat_gemm2 = -1;         // the step's GEMM and cells as a second launch (k_lat_gemm2): -1 where its
+                              // tiles fill the chip once or twice, 1 always, 0 never (in-launch split-K
+                              // tiles); MFGP_LAT_GEMM2, diagnostics and tests
+  bool trinv_columns = false;  // F by the block-column k_trinv_f instead of recursive doubling (MFGP_TRINV_COLUMNS)
+  int factor_depth = 4;        // 64-column steps per trailing-update pass of the factor (MFGP_FACTOR_DEPTH; 1: one-level)
+  bool lat_force = false;     // take it for small batches too (mfgp_ctx_set_lattice(2): tests)
+  // launches of this context may run concurrently with other contexts' (several
+  // streams on one GPU, mfgp_ctx_set_concurrent): no launch may rely on all of its
+  // workgroups being resident at once -- the lattice step's GEMM runs as the second
+  // launch (k_lat_gemm2, no cross-workgroup waits) instead of in-launch split-K tiles
+  bool concurrent = false;
+  int rsplit_force = 0;       // one-pass predict row splits per cell group (0: the host's rule)
+  int lat_zcsr = 1;           // the Z units read member lists built by one scan unit per part
+                              // instead of bucketing every row themselves (MFGP_LAT_ZCSR=0: off)
+  int64_t spin_us = 2000;     // host polling of mapped status words before a synchronise (MFGP_SPIN_US; 0: off)
+  // the eager append of one GP (spec_append_predict) returns at the step's L22
+  // verdict, published by the launch as soon as it is known, instead of at the
+  // launch's end: the caller's host work until its next call (the simulator's
+  // grid check, the predict's argument handling) overlaps the posterior
+  // (MFGP_EARLY_PD=0: wait for the launch's end)
+  bool early_pd = true;
+  bool early_running = false;  // such a launch may still run: the next entry point settles it first
+  bool desc_arg = true;       // a batch step that is one k_inc_lat / k_inc_stream launch passes its
+                              // descriptors by value
+                              // (MFGP_DESC_ARG=0: upload them, diagnostics)
+  // pinned host staging of the status words
+  int* h_status = nullptr;
+  size_t h_status_n = 0;
+  // mfgp_nlml_batch: members per set of launches (0: as many as NLML_BATCH_SCRATCH
+  // holds) and its scratch (NlmlLayout), grown on demand, kept for the next call and
+  // given back by mfgp_ctx_trim
+  int nlml_chunk = 0;
+  double* nb_dev = nullptr;
+  size_t nb_dev_bytes = 0;
+  double* nb_host = nullptr;   // pinned
+  size_t nb_host_bytes = 0;
+
+  int ncu = 256;              // compute units (hipDeviceProp multiProcessorCount)
+  // the path counters of the planners' loops (mfgp_sample_points,
+  // mfgp_batch_sample_points), moved here from the models when each loop ends:
+  // which step form the Choi iterations took (mfgp_ctx_planner_stats)
+  int64_t plan_stats[mfgp_host::PLAN_NSTATS] = {0};
+};
+
+// The look-ahead record of a model (mfgp_query): the border of its last prospective
+// set, keyed by the model's serial and the set's rows and fidelities.
+struct mfgp_look_rec {
+  double* W = nullptr;       // [wld][64]: L^-1 K(X, X_P)
+  int64_t wld = 0;
+  double* L22 = nullptr;     // [64][64] | L22inv [64][64] | ppts [64][2] (one allocation)
+  int* pfid = nullptr;       // [64] fidelities, then the border's status word
+  bool valid = false;        // the border below is stored for (serial, P, key)
+  uint64_t serial = 0;
+  int P = 0;
+  std::vector<double> key;   // the P rows (x, y), then their fidelities
+};
+
+// The sample record of a model (mfgp_sample_posterior): the pivoted-Cholesky factors of
+// the lattice axes' Gram matrices per field, keyed by the model's serial, and the
+// lattice indices of its training rows.
+struct mfgp_sample_rec {
+  bool valid = false;        // the axis factors below belong to `serial`
+  uint64_t serial = 0;
+  int fields = 0, nx = 0, ny = 0;
+  int rx[2] = {0, 0}, ry[2] = {0, 0};
+  double* fac = nullptr;     // device: per field Ax [nx][rx] | AyT [ry][ny]
+  size_t fac_n = 0;          // doubles allocated
+  size_t off_ax[2] = {0, 0}, off_ay[2] = {0, 0};
+  int* lidx = nullptr;       // device [lidx_cap]: px | (py << 16) per training row
+  int64_t lidx_cap = 0;
+  bool lidx_valid = false;   // lidx holds the N rows of `lidx_serial`
+  uint64_t lidx_serial = 0;
+  int64_t off_row = -1;      // the first training row that is no cell of the lattice, or -1
+};
+
+struct mfgp_model {
+  __attribute__((visibility("hidden"))) ~mfgp_model() = default;   // (in two files now: not a symbol of the library)
+  mfgp_ctx* ctx = nullptr;
+  int* gate_dev = nullptr;  // device gate of every step of this model (the planners' loops: 0 = skip)
+  int kind = MFGP_SF;
+  int dtype = MFGP_F64;     // precision of the resident V (MFGP_F32: fp32 storage and stream)
+  int nhyp = 4;
+  double hyp[9] = {0};
+  double jitter = 1e-8;
+  // training set (device)
+  int64_t NL = 0, NH = 0, cap = 0;
+  double* X = nullptr;  // [cap,2]
+  double* y = nullptr;  // [cap]
+  // factor (device)
+  int64_t ld = 0;
+  double* A = nullptr;     // [ld,ld]
+  double* Linv = nullptr;  // [ld/NB][TILE]
+  double* zv = nullptr;     // [cap] z = L^-1 (y - m)
+  double* iscr = nullptr;   // incremental-append scratch (inc_scratch_doubles(cap))
+  int* status = nullptr;
+  int* status_host = nullptr;       // mapped pinned words the single-GP fused launch publishes into:
+                                    // [0] its status (last act), [1] the L22 verdict (pd_host)
+  int* status_host_dev = nullptr;   // its device address
+  bool factored = false;
+  int64_t factor_N = -1;    // rows [0, factor_N) of A / Linv / zv hold the current factor
+  int64_t ablk = 0;         // 64-row blocks of A / Linv initialised (assembled or padded)
+  double factor_hyp[9] = {0};
+  double factor_jitter = 0.0;
+  // grid (device)
+  int64_t M = 0, Mcap = 0;
+  double* grid = nullptr;
+  mfgp::GridLattice lat{};        // lattice structure of the grid (nx == 0: none)
+  std::vector<double> hax, hay;   // the lattice's axis values (host copy, for rows_on_cells)
+  // resident V = L^-1 psi^T [vtiles][vld][PBM] (double, or float for MFGP_F32);
+  // rows [0, v_n) valid for the current factor and grid
+  void* V = nullptr;
+  int64_t vld = 0, vtiles = 0, v_n = 0;
+  double* tred = nullptr;     // [vtiles][2] per-tile (max, argmax) of var, then the tiles' arrival counter
+  int64_t tred_n = 0;         // doubles of tred
+  unsigned* sync = nullptr;   // k_inc_stream hand-off words {arrivals, L21 ready, L22 ready} (zeroed)
+  unsigned epoch = 0;         // last k_inc_stream epoch of this model
+  // the compact bordered rows in iscr (inc_l21c_offset) hold rows [l21c_n0, l21c_N)
+  // bordered onto l21c_n0 factor rows (-1: none)
+  int64_t l21c_n0 = -1, l21c_N = -1;
+  // speculative predict: an (eager) append that follows the pattern append ->
+  // predict runs the bordered append and the one-pass predict as one launch and
+  // keeps mu | var in `spec_out` (mapped pinned, [2][M]) for the predict that
+  // follows; any change to the model drops them
+  double* spec_out = nullptr;
+  double* spec_out_dev = nullptr;
+  int64_t spec_cap = 0;
+  bool spec_valid = false;
+  // spec_out's trailer [2 cap] = (max var, its first argmax) holds the fused var
+  // max / argmax of the launch that wrote spec_out (the eager append's): the
+  // drop-in's np.amax / np.argmax of the covariance read it instead of rescanning
+  bool spec_max = false;
+  bool pred_since_append = false;   // a predict came after the last append
+  // path counters (mfgp_model_stats), indexed by PathCounter
+  int64_t cnt[mfgp_host::N_COUNTERS] = {0};
+  mfgp_look_rec* look = nullptr;   // look-ahead record (allocated by the first mfgp_query, not cloned)
+  mfgp_sample_rec* samp = nullptr;   // sample record (allocated by the first mfgp_sample_*, not cloned)
+  unsigned* csr = nullptr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
+  int64_t csr_n = 0;           // (bytes)
+  // state generation: a new factor from scratch, a new grid or new hyperparameters
+  // start a new one (the resident posterior, F and the tables belong to one)
+  uint64_t gen = 1;
+  // posterior serial (mfgp_model_serial): a process-wide fresh value at every change
+  // of the rows, hyperparameters, jitter or grid -- unlike (gen, N) it never repeats
+  // (truncate + append of the same count), so a holder of an earlier predict's
+  // result can tell whether the model still holds that posterior
+  uint64_t serial = 0;
+  // resident posterior: two buffers [mu | var] of M each, written by every predict
+  // (incremental mode); buffer b holds the posterior of the res_n[b] leading rows
+  double* res = nullptr;
+  int64_t res_M = 0;
+  int64_t res_n[2] = {-1, -1};
+  uint64_t res_gen[2] = {0, 0};
+  int res_depth[2] = {0, 0};   // lattice steps since var / mu were computed from V
+  uint64_t res_tick[2] = {0, 0}, tick = 0;
+  // lattice-separable step state (allocated on first use)
+  double* F = nullptr;        // explicit L^-1 [F_ld][F_ld], rows [0, F_n) current for generation F_gen
+  float* Ff = nullptr;        // MFGP_F32: F in fp32 (the rows the lattice steps stream and extend)
+  int64_t F_ld = 0, F_n = 0;
+  uint64_t F_gen = 0;
+  double* tab = nullptr;      // separable tables [4][tab_ld][tabw], rows [0, tab_n)
+  int64_t tab_ld = 0, tabw = 0, tab_n = 0;
+  uint64_t tab_gen = 0;
+  double* wv = nullptr;       // w [wv_ld][KINC]
+  int64_t wv_ld = 0;
+  unsigned* wflag = nullptr;  // [wv_ld / 64 + 2]
+  unsigned* wcnt = nullptr;   // [wv_ld / 64 + 2]
+  double* wpart = nullptr;    // [LAT_WU_MAX + wv_ld / 64 + 1][1024]
+  double* gpart = nullptr;    // split-K partials
+  size_t gpart_n = 0;
+  unsigned* gcnt = nullptr;   // per GEMM tile
+  int64_t gcnt_n = 0;
+  int* lidx = nullptr;        // lattice indices per training row [tab_ld], rows [0, tab_n) (with the tables)
+  double* axt = nullptr;      // axis tables [4][tabw + 1][tabw], current for generation axt_gen
+  int64_t axt_w = 0;
+  uint64_t axt_gen = 0;
+  double* zb = nullptr;       // Z rows [P][zrows][tabw][zb_ka]
+  int64_t zb_rows = 0, zb_w = 0;
+  int zb_ka = 0;
+  unsigned* zflag = nullptr;  // [zflag_n]
+  int64_t zflag_n = 0;
+  unsigned* ldone = nullptr;  // [4] lattice phase hand-offs (arrivals | flag, twice)
+  int* zvl = nullptr;         // [2][zb_rows + 1]
+  // the column store of V, Vc[cell][vc_ld] in V's element type: rows [0, vc_n) equal V's for
+  // generation vc_gen (allocated with the lattice state where the budget allows: ensure_vcol)
+  void* Vc = nullptr;
+  int64_t vc_ld = 0, vc_M = 0, vc_n = 0;
+  uint64_t vc_gen = 0;
+  int64_t vc_deny_ld = -1, vc_deny_M = -1, vc_deny_budget = -2;   // the shape and budget last refused
+};
+
+namespace mfgp_host __attribute__((visibility("hidden"))) {
+
+inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// An eager append that returned at its L22 verdict (mfgp_ctx::early_pd) may still
+// run: every entry point waits for it, and takes its status, before it reads or
+// reuses anything the launch touches.
+inline int settle(mfgp_ctx* c) { return (c && c->early_running) ? mfgp_ctx_synchronize(c) : MFGP_OK; }
+
+int check_model(const mfgp_model* m);
+
+// The opening of an entry point on one model: the context's device (restored when the
+// entry point returns), then the running eager append settled, then the model checked;
+// rc is the first failure of the two.
+struct Entry {
+  const DeviceGuard dg_;
+  int rc;
+  explicit Entry(const mfgp_model* m) : dg_(m ? m->ctx->device : -1), rc(settle(m ? m->ctx : nullptr)) {
+    if (rc == MFGP_OK) rc = check_model(m);
+  }
+};
+
+// Small buffers that every GEMM workgroup of the lattice step reads (the axis
+// tables, the member lists): whole 2 MiB units, so that they sit in one large page
+inline hipError_t hip_malloc_2m(void** p, size_t bytes) {
+  const size_t unit = size_t(2) << 20;
+  return hipMalloc(p, (bytes + unit - 1) / unit * unit);
+}
+
+// A device buffer replaced by a fresh one of `bytes` once the stream has drained (its
+// launches may read the old one); zeroed on the stream when `zero`, in whole 2 MiB
+// units when `big_page`. p is null if the allocation fails.
+template <class T>
+int renew(hipStream_t s, T*& p, size_t bytes, bool zero, bool big_page = false) {
+  HIP_TRY(hipStreamSynchronize(s));
+  if (p) HIP_TRY(hipFree(p));
+  p = nullptr;
+  HIP_TRY(big_page ? hip_malloc_2m(reinterpret_cast<void**>(&p), bytes) : hipMalloc(&p, bytes));
+  if (zero) HIP_TRY(hipMemsetAsync(p, 0, bytes, s));
+  return MFGP_OK;
+}
+
+// Offsets of the pieces of a workspace, in the order they are taken, each rounded up
+// to 256 bytes; `end` is the room they need.
+struct WsLayout {
+  size_t end = 0;
+  static size_t up(size_t bytes) { return (bytes + 255) / 256 * 256; }
+  size_t take(size_t bytes) {
+    const size_t at = end;
+    end += up(bytes);
+    return at;
+  }
+};
+
+// An output matrix of `cols` columns that the caller may hold in host memory: the
+// kernels write `dev` with leading dimension `ld` -- the caller's buffer and ldo when
+// it is device memory, else the packed image at `stage` (workspace), which copy_back
+// enqueues into the caller's buffer. The caller synchronises.
+struct StagedOut {
+  double* dev;
+  int64_t ld;
+  double* user;   // the host buffer copy_back fills (null: nothing to copy)
+  int64_t user_ld;
+  StagedOut(double* out, int64_t ldo, bool host, void* stage, int64_t cols)
+      : dev(host ? static_cast<double*>(stage) : out), ld(host ? cols : ldo), user(host ? out : nullptr), user_ld(ldo) {}
+  hipError_t copy_back(int64_t cols, int64_t rows, hipStream_t s) const {
+    if (!user) return hipSuccess;
+    return hipMemcpy2DAsync(user, sizeof(double) * user_ld, dev, sizeof(double) * ld, sizeof(double) * cols, rows,
+                            hipMemcpyDeviceToHost, s);
+  }
+};
+
+// table width of the lattice step: 64, 128, 192 or 256 where the step applies (lat_eligible:
+// <= NT). At 192 zq rounds down to 2 and a Z unit's second thread group is a partial one
+// (lat_zunit); every width, rectangles and a degenerate axis: tests/test_gpu_lattice_grids.py
+inline int64_t lat_tabw(const mfgp_model* m) { return round_up(std::max<int64_t>(m->lat.nx, m->lat.ny), 64); }
+
+// mfgp_capi.hip: state
+void bump_serial(mfgp_model* m);
+mfgp::Hyp derive_hyp(int kind, const double* hyp, double jitter);
+int ensure_h_status(mfgp_ctx* c, size_t n);
+int ensure_ws(mfgp_ctx* c, size_t bytes);
+int ensure_cap(mfgp_model* m, int64_t need);
+int ensure_v(mfgp_model* m);
+void fill_desc(mfgp::GPDesc& d, mfgp_model* m);
+double* res_mu(mfgp_model* m, int b);
+double* res_var(mfgp_model* m, int b);
+int res_find(const mfgp_model* m, int64_t n);
+void res_tag(mfgp_model* m, int b, int64_t n, int depth);
+int set_res_out(mfgp_model* m, mfgp::GPDesc& d, int keep);
+int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu);
+int ensure_vcol(mfgp_model* m);
+int64_t vcol_rows(const mfgp_model* m);
+int status_error(int st);
+int read_status(mfgp_model* m);
+int ensure_spec_out(mfgp_model* m);
+bool factor_current(const mfgp_model* m);
+bool can_inc_factor(const mfgp_model* m);
+bool can_vstream(const mfgp_model* m);
+bool is_device_ptr(const void* p);
+int copy_rows(mfgp_model* m, int64_t at, const double* X, const double* y, int64_t k);
+
+// mfgp_step.hip: descriptor slots, launches, the batch step
+mfgp::GPDesc* acquire_slot(mfgp_ctx* c, int& slot, int& rc);
+int upload_slot(mfgp_ctx* c, int slot, int count, const mfgp::GPDesc** dptr);
+int release_slot(mfgp_ctx* c, int slot);
+int enqueue_factor(mfgp_ctx* c, const mfgp::GPDesc* dd, const mfgp::GPDesc* hd, int count);
+int enqueue_vstream(mfgp_ctx* c, const mfgp::GPDesc* dd, const mfgp::GPDesc* hd, int count);
+int enqueue_predict(mfgp_ctx* c, const mfgp::GPDesc* dd, const mfgp::GPDesc* hd, int count);
+int assign_predict_scratch(mfgp_ctx* c, mfgp::GPDesc* hd, int count);
+void set_rsplit(const mfgp_ctx* c, mfgp::GPDesc* hd, int count);
+void mark_inc_factor(mfgp_model* m);
+int fill_inc_desc(mfgp::GPDesc& d, mfgp_model* m);
+void set_vstream_rows(mfgp::GPDesc& d, const mfgp_model* m);
+int factor_one(mfgp_model* m);
+int update_factor(mfgp_model* m);
+int batch_run(mfgp_model** models, int count, const double* X, const double* y, const int64_t* k, double* mu,
+              double* var, double* vmax, int64_t* vargmax, int flags, bool do_factor, bool do_predict,
+              const int64_t* out_offs = nullptr, const int* vidx = nullptr);
+
+// mfgp_train.hip
+int free_nlml_scratch(mfgp_ctx* c);
+
+}  // namespace mfgp_host
+
+// (an exported symbol of the library since the eager append: kept)
+extern "C" int spec_append_predict(mfgp_model* m, const double* X, const double* y, int64_t k);

@@ -1,6 +1,6 @@
 """The full-path factor and the lattice step's explicit inverse (round 3).
 
-- Two-level blocked Cholesky (mfgp_capi.hip enqueue_factor, k_syrk_blk): the
+- Two-level blocked Cholesky (mfgp_step.hip enqueue_factor, k_syrk_blk): the
   trailing matrix takes a group of 64-column steps in one pass. The MFMA
   sequence per tile is the one-level factor's, so L, mu and var must be
   bit-equal to MFGP_FACTOR_DEPTH=1 for every group depth, on a ragged batch.

@@ -25,7 +25,7 @@ from oracle import gp_oracle as O
 pytestmark = pytest.mark.gpu
 
 TOL = O.PARITY_TOL
-MAXD = 256   # mfgp_capi.hip LAT_MAXD
+MAXD = 256   # mfgp_host.h LAT_MAXD
 CHECK = (1, 128, 256, 257, 258, 300)
 
 

@@ -27,8 +27,8 @@ from tests import _fixtures as F
 pytestmark = pytest.mark.gpu
 
 TOL = O.PARITY_TOL
-RMAX = 1e4   # mfgp_capi.hip LAT_RMAX: the conditioning gate
-MAXD = 256   # mfgp_capi.hip LAT_MAXD
+RMAX = 1e4   # mfgp_host.h LAT_RMAX: the conditioning gate
+MAXD = 256   # mfgp_host.h LAT_MAXD
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -40,7 +40,7 @@ def lattice_forced():
 
 
 def _gate_ok(hyp):
-    """The host's conditioning gate (mfgp_capi.hip lat_cond_ok)."""
+    """The host's conditioning gate (mfgp_step.hip lat_cond_ok)."""
     h = np.asarray(hyp)
     if h.shape[0] == 4:
         noise = np.exp(h[3])

@@ -5,8 +5,13 @@ unit's share is within one step of the others', a block's partial slots never
 collide, and the host's partial buffer (LAT_WU_MAX + nwb slots) holds them.
 CPU only: the device's own result is checked by the -m gpu lattice tests
 (test_gpu_lattice.py::test_lattice_split_and_w_units_vs_oracle)."""
+import os
+import shutil
+import subprocess
+
 import pytest
 
+HERE = os.path.dirname(os.path.abspath(__file__))
 LAT_WU_MAX = 512
 LAT_NWB_MAX = 256
 
@@ -87,14 +92,42 @@ def test_w_unit_partition(n0, U):
     assert max(slots) < LAT_WU_MAX + nwb                   # fits the host's partial buffer
 
 
-def test_host_unit_counts_share_the_launch():
-    """The host's rule (mfgp_capi.hip): two units per CU over the launch, each GP's
-    count by its F steps, clamped to [1, min(LAT_WU_MAX, steps)]."""
+def test_host_unit_counts_share_the_launch(tmp_path):
+    """The host's rule itself (csrc/mfgp_lat_plan.h, which mfgp_step.hip's plan_lat calls),
+    compiled into a stand-alone program (tests/lat_plan_main.cpp) and run here: each GP's
+    count by its F steps, clamped to [1, min(LAT_WU_MAX, steps)], at a total of 512; and
+    the plans DESIGN.md section 2.4 states for 256 CUs without override knobs -- the
+    headline batch (8 MF GPs, 128 x 128, n0 = 2040) runs its GEMM as the second launch
+    over 256 tiles with 64 w units per GP, one such GP keeps the in-launch tiles with
+    264 units, and configs[4] (32 GPs, 256 x 256, n0 = 8184, fp32 V) keeps them with 2048."""
+    import __graft_entry__ as ge
+    exe = tmp_path / "lat_plan"
+    cxx = shutil.which("c++") or shutil.which("g++") or ge.HIPCC
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I", ge.CSRC, os.path.join(HERE, "lat_plan_main.cpp"),
+                    "-o", str(exe)], check=True, capture_output=True)
+
+    def run(*cases):
+        out = subprocess.run([str(exe), *cases], check=True, capture_output=True, text=True).stdout
+        return [line.split() for line in out.splitlines()]
+
     def counts(n0s, total=512):
-        st = [lat_wsteps(n) for n in n0s]
-        tot = sum(st)
-        return [max(1, min((total * s + tot // 2) // tot, LAT_WU_MAX, s)) for s in st]
+        (line,) = run("share:%d:%s" % (total, ",".join(str(n) for n in n0s)))
+        assert line[0] == "share" and len(line) == 1 + len(n0s)
+        return [int(v) for v in line[1:]]
     assert counts([2040] * 8) == [64] * 8
     assert counts([2040]) == [512]
     assert sum(counts([2040] * 32)) == 512
     assert counts([10, 2040]) == [1, 512]
+
+    def plan(ncu, B, n0, k, M, es, nx, ny, sf=0):
+        (line,) = run("plan:" + ":".join(str(v) for v in (ncu, B, n0, k, M, es, nx, ny, sf)))
+        assert line[0] == "plan"
+        return {kv.split("=")[0]: int(kv.split("=")[1]) for kv in line[1:]}
+    for k in (1, 8):
+        p = plan(256, 8, 2040, k, 128 * 128, 8, 128, 128)
+        assert (p["take"], p["ka"], p["g2"], p["ksplit"]) == (1, 8, 1, 1), p
+        assert (p["tiles"], p["wu_total"], p["nwu"]) == (256, 512, 64), p
+        p = plan(256, 1, 2040, k, 128 * 128, 8, 128, 128)
+        assert (p["take"], p["g2"], p["wu_total"], p["nwu"]) == (1, 0, 264, 264), p
+        p = plan(256, 32, 8184, k, 256 * 256, 4, 256, 256)
+        assert (p["take"], p["g2"], p["wu_total"]) == (1, 0, 2048), p

@@ -1,14 +1,14 @@
 #!/bin/bash
-# Diagnostic library variants (same sources, different -D switches) into build/.
+# Diagnostic library variants (same sources, different -D switches) into build/,
+# built as the library itself is (__graft_entry__.build: its source list and flags).
 # usage: tools/build_variants.sh NAME "-DFLAG=.. -DFLAG2=.." [NAME2 "FLAGS2" ...]
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
-C=$R/mfgp_coverage_amd/csrc
-mkdir -p $R/build
+mkdir -p "$R/build"
 while [ $# -ge 2 ]; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC $2 -o $R/build/libmfgp_$1.so \
-    $C/mfgp_kernels.hip $C/mfgp_cells.hip $C/mfgp_nlml.hip $C/mfgp_capi.hip &
+  (cd "$R" && python -c 'import shlex, sys, __graft_entry__ as g
+g.build(extra=shlex.split(sys.argv[2]), out=sys.argv[1])' "$R/build/libmfgp_$1.so" "$2") &
   shift 2
 done
 wait
-ls -la $R/build
+ls -la "$R/build"

@@ -55,7 +55,7 @@ used = tr[:, 0] > 0
 t0 = tr[used, 0].min()
 tr = np.where(tr > 0, (tr - t0) / 100.0, np.nan)   # us (100 MHz realtime counter)
 nprod, nwb = 16, 32
-# the host's rule (mfgp_capi.hip): two w units per CU over the batch (MFGP_LAT_WU: the
+# the host's rule (mfgp_lat_plan.h): two w units per CU over the batch (MFGP_LAT_WU: the
 # total), each GP's count by its F steps (equal n0 here)
 n0 = NL + NH0
 C16 = (n0 + 15) // 16
