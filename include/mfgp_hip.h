@@ -250,6 +250,28 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
 #define MFGP_IVR_MAXW 8
 int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
                        double* out, int64_t ldo, double* best, int64_t* best_pos);
+/* The posterior covariance applied to grid vectors,
+ *   out[k * ldo + i] = sum_j cov(i, j) x[k * ldx + j],   i, j over all M cells, k < nx,
+ * for nx <= MFGP_IVR_MAXW vectors, from the resident V: cov x = K** x - V^T (V x), two
+ * streamed passes over V per vector (k_cov_dot, k_cov_apply) and the prior's product, so
+ * the M x M matrix never exists -- the one covariance quantity a grid too large for
+ * mfgp_cov_block's dense block still gives (w^T cov w: the variance of the field's mass
+ * over a region). K** x: on a lattice grid with axes of at most 256 values the kernel
+ * factorises over the axes and the product is two small matrix products per kernel
+ * part; on any other grid k** is evaluated entry by entry (M^2 exponentials: meant for
+ * grids of a few thousand cells). The two forms agree to rounding, not bit for bit;
+ * the environment variable MFGP_PLAN_SEP=0 (read at mfgp_ctx_create) forces the second.
+ * x: [nx][ldx], ldx >= M; out: [nx][ldo], ldo >= M; each host or device memory.
+ * flags: MFGP_COV_PRIOR = K** x alone (no factor needed); a model without training
+ * rows gives the same. The call settles the model as mfgp_cov_block does
+ * (MFGP_ERR_NOT_PD, MFGP_ERR_NO_V as there) and validates everything before anything
+ * is enqueued: a model without a grid, an MFGP_F32 model, nx outside
+ * [1, MFGP_IVR_MAXW], ldx < M, ldo < M, a null pointer and a non-finite value in a host
+ * x return MFGP_ERR_ARG, launch nothing and leave the model as it was. The model
+ * itself is not changed (serial, counters, V and posterior stay). The vectors run one
+ * after another: out's row k depends bit for bit only on the model and x's row k -- not
+ * on nx, k or the other rows -- and two calls agree bit for bit. */
+int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* out, int64_t ldo, int flags);
 /* The model's posterior serial: a value that changes whenever its training rows,
  * hyperparameters, jitter or grid change (appends, the batch entry points,
  * mfgp_truncate, mfgp_set_data / _set_hyp / _set_grid, the planners' loops), and is
@@ -417,6 +439,41 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
  * call, and points / counts are unspecified. */
 int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thresholds, int64_t max_points,
                              double* points, int64_t* counts);
+/* The greedy integrated-variance planner: up to n_points grid cells chosen one after
+ * another, each the allowed cell c that maximises the A-optimal score of
+ * mfgp_var_reduction under one weight vector,
+ *   sum_i w[i] cov_t(i, c)^2 / (cov_t(c, c) + noise_H + jitter),
+ * where cov_t is the posterior covariance given the model's rows and the t cells
+ * chosen before (each taken as a hifi row with the posterior mean at the cell as its
+ * pseudo-observation). A pick changes the covariance by a rank-one term, so the scores
+ * follow from one product of the covariance with a grid vector per pick (two streamed
+ * passes over the resident V, mfgp_cov_apply's kernels) instead of mfgp_var_reduction's
+ * GEMM: that GEMM runs once per call, and again after every `refresh` picks when
+ * refresh > 0 (the numerators recomputed from scratch on the current rows: for long
+ * runs, and the cross-check of the recurrence; 0 = never). w: [>= M] weights, ldw >= M,
+ * host or device memory, NULL = ones. cand: a host array of the nc allowed cells in
+ * [0, M), NULL = all cells (then nc must equal M); no other cell is ever chosen; among
+ * equal scores the first position in the list wins, and a NaN score never does. The run
+ * stops after n_points picks or before the first pick whose score is < min_gain. Outputs
+ * (host memory): cells [n_points] the grid indices, points [n_points][2] their
+ * coordinates, gains [n_points] each pick's score at the time it was chosen, *count the
+ * number of picks. The loop runs on the model itself, past its own rows, in chunks of up
+ * to 32 iterations behind a device gate with one status read per chunk, as
+ * mfgp_sample_points; each append is the general batch step of one model (the lattice
+ * step where its gates take it, else the fused V stream). The call settles the model as
+ * mfgp_cov_block does (MFGP_ERR_NOT_PD, MFGP_ERR_NO_V as there) and validates everything
+ * before anything is enqueued: a model without a grid, an MFGP_F32 model, ldw < M, a cell
+ * outside [0, M), a non-finite weight in a host w, n_points < 0, refresh < 0, a null
+ * output and a context with incremental updates disabled return MFGP_ERR_ARG, launch
+ * nothing and leave the model as it was. n_points == 0 or nc == 0: MFGP_OK, *count = 0.
+ * Afterwards -- and after any error, MFGP_ERR_NOT_PD from a step of the loop included --
+ * the model is as the settling left it: its rows, its predict's bits and its path
+ * counters (the loop's steps are counted in mfgp_ctx_planner_stats), and its next step
+ * gives the bits of a model that never ran the planner. Two calls return the same cells
+ * and the same gains bit for bit. */
+int mfgp_plan_ivr(mfgp_model* m, const double* w, int64_t ldw, const int64_t* cand, int64_t nc,
+                  int64_t n_points, double min_gain, int refresh,
+                  int64_t* cells, double* points, double* gains, int64_t* count);
 /* Keep only the first n_keep_hifi hifi rows (no refactor; benchmark reset). */
 int mfgp_truncate(mfgp_model* m, int64_t n_keep_hifi);
 /* mfgp_truncate of count models with one call (the benchmark's per-step reset). */

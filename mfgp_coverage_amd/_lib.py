@@ -91,6 +91,11 @@ SIGNATURES = {
     "mfgp_var_reduction": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "mfgp_cov_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "mfgp_plan_ivr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int64_p]),
     "mfgp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
@@ -517,6 +522,95 @@ class Model:
         if two:
             return res, bv[:nw], bp[:nw]
         return res, np.float64(bv[0]), int(bp[0])
+
+    def cov_apply(self, x, out=None, prior=False):
+        """The posterior covariance applied to grid vectors (mfgp_cov_apply): cov @ x from the
+        resident V in two streamed passes per vector, without the M x M matrix. x: a float64
+        ndarray [M] or [k, M] with k <= IVR_MAXW (row k one vector), or a device tensor of
+        that shape (data_ptr(), shape, stride(); unit column stride). Returns the same shape;
+        out: a host float64 array or a device tensor of that shape to fill in place (a
+        device out returns None). prior: K** @ x alone. Settles the model as cov_block() does
+        and leaves it unchanged; a row's bits depend only on the model and that row of x."""
+        L = lib()
+        M = L.mfgp_model_m(self.handle)
+
+        def dev2(t, what):
+            shape, stride = tuple(t.shape), tuple(t.stride())
+            if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) not in (1, 2) or \
+                    (shape[-1] > 1 and stride[-1] != 1):
+                raise ValueError(f"{what} must be a float64 tensor [M] or [k, M] with unit column stride")
+            two = len(shape) == 2
+            ld = int(stride[0]) if two and shape[0] > 1 else int(shape[-1])
+            return ctypes.c_void_p(int(t.data_ptr())), (int(shape[0]) if two else 1), int(shape[-1]), ld, two
+        if hasattr(x, "data_ptr"):
+            xp, nx, xn, ldx, two = dev2(x, "x")
+        else:
+            xa = np.asarray(x, dtype=np.float64)
+            if xa.ndim not in (1, 2):
+                raise ValueError(f"x must be [M] or [k, M] with M = {M}")
+            two = xa.ndim == 2
+            xa = np.ascontiguousarray(xa.reshape(-1, xa.shape[-1]))
+            xp, nx, xn, ldx = ctypes.c_void_p(xa.ctypes.data), xa.shape[0], xa.shape[1], xa.shape[1]
+        if xn != M:
+            raise ValueError(f"x must have M = {M} columns (got {xn})")
+        flags = COV_PRIOR if prior else 0
+        if out is not None and hasattr(out, "data_ptr"):
+            o_p, orows, ocols, ldo, otwo = dev2(out, "out")
+            if otwo != two or orows < nx or ocols < M:
+                raise ValueError("out must have the shape of x")
+            check(L.mfgp_cov_apply(self.handle, xp, nx, ldx, o_p, ldo, flags))
+            return None
+        if out is None:
+            buf = np.empty((nx, M), dtype=np.float64)
+        else:
+            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != (2 if two else 1) or \
+                    out.strides[-1] != 8 or not out.flags.writeable or out.shape[-1] < M or \
+                    (two and (out.shape[0] < nx or out.strides[0] % 8)):
+                raise ValueError("out must be a writable float64 array of x's shape")
+            buf = out if two else out.reshape(1, -1)
+        ldo = int(buf.strides[0] // 8) if buf.shape[0] > 1 else int(buf.shape[1])
+        check(L.mfgp_cov_apply(self.handle, xp, nx, ldx, ctypes.c_void_p(buf.ctypes.data), ldo, flags))
+        return buf[:nx, :M] if two else buf[0, :M]
+
+    def plan_ivr(self, n_points, weights=None, cand=None, min_gain=0.0, refresh=0):
+        """The greedy integrated-variance planner (mfgp_plan_ivr): up to n_points grid cells,
+        each the allowed cell with the largest var_reduction() score given the picks before
+        it -> (cells [n] int64, points [n, 2], gains [n]); gains[t] is pick t's score when it
+        was chosen. weights: None (ones) or [>= M], a float64 ndarray or a device tensor.
+        cand: the allowed cells (None = all). The run stops before the first pick whose
+        score is < min_gain. refresh = R > 0: the numerators are recomputed from scratch after
+        every R picks. The model is unchanged; its loop is counted in Context.planner_stats()."""
+        L = lib()
+        M = L.mfgp_model_m(self.handle)
+        n_points = int(n_points)
+        if cand is None:
+            cp, nc = None, M
+        else:
+            ca = np.ascontiguousarray(np.asarray(cand).reshape(-1), dtype=np.int64)
+            cp, nc = ctypes.c_void_p(ca.ctypes.data), ca.shape[0]
+        if weights is None:
+            wp, ldw = None, M
+        elif hasattr(weights, "data_ptr"):
+            shape, stride = tuple(weights.shape), tuple(weights.stride())
+            if str(getattr(weights, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) != 1 or \
+                    (shape[0] > 1 and stride[0] != 1):
+                raise ValueError("weights must be a contiguous float64 tensor [>= M]")
+            wp, ldw = ctypes.c_void_p(int(weights.data_ptr())), int(shape[0])
+        else:
+            wa = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if wa.ndim != 1:
+                raise ValueError(f"weights must be [>= M] with M = {M}: one weight vector")
+            wp, ldw = ctypes.c_void_p(wa.ctypes.data), wa.shape[0]
+        P = max(n_points, 1)
+        cells = np.empty(P, dtype=np.int64)
+        pts = np.empty((P, 2), dtype=np.float64)
+        gains = np.empty(P, dtype=np.float64)
+        n = ctypes.c_int64(0)
+        check(L.mfgp_plan_ivr(self.handle, wp, ldw, cp, nc, n_points, float(min_gain), int(refresh),
+                              ctypes.c_void_p(cells.ctypes.data), ctypes.c_void_p(pts.ctypes.data),
+                              ctypes.c_void_p(gains.ctypes.data), ctypes.byref(n)))
+        k = int(n.value)
+        return cells[:k].copy(), pts[:k].copy(), gains[:k].copy()
 
     def query(self, Xq, XL_new=None, XH_new=None, mu=True, var0=False, var=True, cov=False, ldc=None):
         """The posterior at arbitrary points Xq [n, 2], optionally with prospective lofi /

@@ -638,6 +638,7 @@ int mfgp_ctx_create(int device, mfgp_ctx** out) {
     c->lat_vcol = (e[0] == 'a' || v < 0) ? -1 : (v != 0 ? 1 : 0);
   }
   if (const char* e = std::getenv("MFGP_LAT_GEMM2")) c->lat_gemm2 = std::atoi(e) != 0 ? 1 : 0;
+  if (const char* e = std::getenv("MFGP_PLAN_SEP")) c->plan_sep = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("MFGP_TRINV_COLUMNS")) c->trinv_columns = std::atoi(e) != 0;
   if (const char* e = std::getenv("MFGP_FACTOR_DEPTH")) c->factor_depth = std::max(1, std::min(16, std::atoi(e)));
   // A/B runs: MFGP_LATTICE = 0 (V stream only), 1 (default), 2 (lattice without the size gate)

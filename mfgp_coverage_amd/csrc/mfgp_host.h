@@ -162,6 +162,8 @@ struct mfgp_ctx {
   int rsplit_force = 0;       // one-pass predict row splits per cell group (0: the host's rule)
   int lat_zcsr = 1;           // the Z units read member lists built by one scan unit per part
                               // instead of bucketing every row themselves (MFGP_LAT_ZCSR=0: off)
+  int plan_sep = 1;           // the covariance products take the separable K** x on lattice grids
+                              // (MFGP_PLAN_SEP=0: always the general form; tests)
   int64_t spin_us = 2000;     // host polling of mapped status words before a synchronise (MFGP_SPIN_US; 0: off)
   // the eager append of one GP (spec_append_predict) returns at the step's L22
   // verdict, published by the launch as soon as it is known, instead of at the
@@ -457,6 +459,26 @@ int update_factor(mfgp_model* m);
 int batch_run(mfgp_model** models, int count, const double* X, const double* y, const int64_t* k, double* mu,
               double* var, double* vmax, int64_t* vargmax, int flags, bool do_factor, bool do_predict,
               const int64_t* out_offs = nullptr, const int* vidx = nullptr);
+
+// mfgp_resident.hip
+bool all_finite(const double* p, int64_t n);
+int ensure_resident_v(mfgp_model* m, const char* who);
+// The scratch and the fixed arguments of covariance products u = K** x - V^T (V x) on
+// m's grid (mfgp_plan_ivr.hip): laid out at `base` (cov_work_bytes(m, rows) bytes, 256-byte
+// aligned, for a V of at most `rows` rows). cov_work_init enqueues the axis Gram matrices
+// of the separable K** x where the grid is a lattice it serves; cov_work_run enqueues one
+// product from the model's current V (a.x, a.u or a.S / a.g / a.tau_part / a.ntau and
+// a.gate set by the caller; n_rows: the rows of V that enter).
+struct CovWork {
+  mfgp::CovApply a;
+  mfgp::KssArgs k;
+  bool sep = false;
+  double* T = nullptr;
+  double* kx = nullptr;
+};
+size_t cov_work_bytes(const mfgp_model* m, int64_t rows);
+int cov_work_init(mfgp_model* m, char* base, int64_t rows, CovWork& w);
+int cov_work_run(mfgp_model* m, CovWork& w, int64_t n_rows);
 
 // mfgp_train.hip
 int free_nlml_scratch(mfgp_ctx* c);

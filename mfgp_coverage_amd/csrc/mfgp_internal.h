@@ -287,6 +287,70 @@ inline int64_t ivr_finish_blocks(int64_t nc) { return (nc + NT - 1) / NT; }
 hipError_t launch_ivr(const GPDesc& d, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
                       double* partial, double* out, int64_t ldo, double* bval, int64_t* bpos, double* best,
                       int64_t* best_pos, hipStream_t s);
+// k_ivr_partial alone: the numerators' partial sums partial[ivr_segments(M)][nw][nc], undivided
+hipError_t launch_ivr_partial(const GPDesc& d, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
+                              double* partial, hipStream_t s);
+// The posterior covariance applied to a grid vector from the resident V, u = K** x - V^T (V x)
+// (k_cov_dot, k_cov_psum, k_cov_apply; mfgp_plan_ivr.hip), and the greedy
+// integrated-variance planner's kernels on top of it.
+constexpr int COV_SEG = 8;    // 64-cell tiles per cell segment of k_cov_dot (one partial of p each)
+constexpr int COV_RC = 64;    // training rows per k_cov_dot workgroup
+inline int64_t cov_segments(int64_t M) { return (ntiles_grid(M) + COV_SEG - 1) / COV_SEG; }
+inline int64_t plan_tau_parts(int64_t M) { return (M + NT - 1) / NT; }   // k_plan_x workgroups
+constexpr int KSS_AXIS_MAX = 256;   // longest lattice axis the separable K** x serves
+struct CovApply {
+  const double* V;        // resident V [tiles][vld][64]
+  int64_t vld, N, M;      // N rows enter (0: the prior's product)
+  const double* grid;     // [M,2]
+  Hyp h;
+  const double* x;        // [M]
+  double* part;           // pass A: [cov_segments(M)][pld]
+  int64_t pld;            // >= N
+  double* p;              // [>= N] V x
+  const double* kx;       // K** x [M] (k_kss_out), or null: pass B evaluates the general form
+  double* u;              // stand-alone form: u [M], or null
+  double* S;              // planner's form (or null): S(c) -= 2 g(c) u(c) + g(c)^2 tau
+  const double* g;        // [M]
+  const double* tau_part; // [ntau], tau = their sum in order
+  int ntau;
+  const int* gate;        // device gate (null: always run)
+};
+// the separable K** x of a lattice grid: the axis Gram matrices ax [parts][nx][nx],
+// ay [parts][ny][ny] at unit scale (part 0: l_L, part 1: l_H, MF only)
+struct KssArgs {
+  const double* grid;
+  int nx, ny, parts;
+  int64_t sx, sy;
+  Hyp h;
+  double* ax;
+  double* ay;
+};
+struct PlanPick {
+  const double* S;        // [M] numerators
+  const double* var;      // [M] the current diagonal
+  const double* mu;       // [M] the current mean
+  const double* grid;     // [M,2]
+  const int64_t* cand;    // allowed cells [nc], or null = 0..M-1 (nc = M)
+  int64_t nc;
+  double noise, jitter;   // the denominator's sigma_H and jitter
+  double min_gain;
+  int64_t n_points;
+  int64_t* state;         // {gate (an int), count}
+  const int* status;      // the model's status word
+  double* xn;             // [2] the next hifi row's coordinates
+  double* yn;             // [1] its pseudo-observation
+  int64_t* cells;         // [n_points]
+  double* gains;          // [n_points]
+  double* pts;            // [n_points][2]
+};
+hipError_t launch_kss_axes(const KssArgs& k, hipStream_t s);
+// T: scratch [parts][nx * ny]
+hipError_t launch_kss(const KssArgs& k, const double* x, double* T, double* out, const int* gate, hipStream_t s);
+hipError_t launch_cov_apply(const CovApply& a, hipStream_t s);
+hipError_t launch_plan_x(const double* V, int64_t vld, int64_t row, int64_t M, const double* w, double* g, double* x,
+                         double* tau_part, const int* gate, hipStream_t s);
+hipError_t launch_plan_ssum(const double* partial, int nseg, int64_t M, double* S, hipStream_t s);
+hipError_t launch_ivr_pick(const PlanPick& q, hipStream_t s);
 // look-ahead variance and off-grid queries (k_look_border, k_look_query; mfgp_look.hip).
 // The factor side is the model's (A, Linv, zv for its N rows, current for h); the
 // record side (W, L22, L22inv, ppts, pfid, status) is the model's look-ahead record.

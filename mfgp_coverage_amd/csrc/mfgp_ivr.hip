@@ -234,14 +234,20 @@ __global__ __launch_bounds__(NT) void k_ivr_best(const double* __restrict__ bval
   }
 }
 
+hipError_t launch_ivr_partial(const GPDesc& d, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
+                              double* partial, hipStream_t s) {
+  if (nc <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)ivr_segments(d.M));
+  hipLaunchKernelGGL(k_ivr_partial, grid, dim3(NT), 0, s, d, cand, nc, w, nw, ldw, partial);
+  return hipGetLastError();
+}
+
 hipError_t launch_ivr(const GPDesc& d, const int64_t* cand, int64_t nc, const double* w, int nw, int64_t ldw,
                       double* partial, double* out, int64_t ldo, double* bval, int64_t* bpos, double* best,
                       int64_t* best_pos, hipStream_t s) {
   if (nc <= 0) return hipSuccess;
   const int nseg = (int)ivr_segments(d.M);
-  const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)nseg);
-  hipLaunchKernelGGL(k_ivr_partial, grid, dim3(NT), 0, s, d, cand, nc, w, nw, ldw, partial);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_ivr_partial(d, cand, nc, w, nw, ldw, partial, s);
   if (e != hipSuccess) return e;
   const int64_t nblk = ivr_finish_blocks(nc);
   hipLaunchKernelGGL(k_ivr_finish, dim3((unsigned)nblk), dim3(NT), 0, s, d, cand, nc, partial, nseg, nw, out, ldo,

@@ -417,6 +417,193 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   return sync_ok ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "batch_sample_points: restore failed");
 }
 
+// The greedy integrated-variance planner (mfgp_plan_ivr.hip): n_points cells chosen one
+// after another, each the allowed cell whose measurement lowers the weighted posterior
+// variance of the whole grid most, given the picks before it. Each iteration is
+// k_ivr_pick (argmax of S / (var + sigma_H + jitter), the cell and its posterior mean
+// -> the next hifi row, or the gate closed), the general batch step of one model on
+// that row (the lattice step where its gates take it, else the fused V stream), then
+// the rank-one update of the numerators S from one covariance product over the
+// resident V (k_plan_x, k_cov_dot, k_cov_psum, the K** x term, k_cov_apply). S_0 (and
+// every `refresh` picks, S again) is k_ivr_partial's numerators over all cells: the
+// only GEMM. Chunks of iterations are enqueued behind the device gate with one status
+// read per chunk, on the caller's model (plan_enter / plan_leave), as
+// mfgp_sample_points; a chunk ends where a refresh is due.
+int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t* cand, int64_t nc,
+                  int64_t n_points, double min_gain, int refresh, int64_t* cells, double* points, double* gains,
+                  int64_t* count) {
+  const Entry entry(model);
+  int rc = entry.rc;
+  if (rc) return rc;
+  mfgp_model* t = model;
+  mfgp_ctx* c = t->ctx;
+  const int64_t M = t->M;
+  if (!count) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: null count");
+  if (n_points < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative n_points");
+  if (refresh < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative refresh");
+  if (n_points > 0 && (!cells || !points || !gains)) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: null output");
+  if (t->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
+  if (M <= 0 || !t->grid) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the model has no grid (mfgp_set_grid)");
+  if (!c->incremental) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr needs incremental updates enabled");
+  if (w && ldw < M)
+    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: ldw = %lld is less than M = %lld", (long long)ldw, (long long)M);
+  if (nc < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative candidate count");
+  if (!cand && nc != M)
+    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: a NULL candidate list means all %lld cells (got nc = %lld)",
+                   (long long)M, (long long)nc);
+  for (int64_t j = 0; cand && j < nc; ++j)
+    if (cand[j] < 0 || cand[j] >= M)
+      return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: cand[%lld] = %lld is outside the grid's cells [0, %lld)",
+                     (long long)j, (long long)cand[j], (long long)M);
+  const bool w_host = w && !is_device_ptr(w);
+  if (w_host && !all_finite(w, M)) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the weights must be finite");
+  if (ivr_segments(M) > 65535)
+    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: grids of at most %lld cells are supported",
+                   (long long)65535 * IVR_SEG * PBM);
+  *count = 0;
+  if (n_points == 0 || nc == 0) return MFGP_OK;
+  // earlier ASYNC steps' verdicts first: the loop's decisions read the status word
+  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
+  if ((rc = update_factor(t))) return rc;
+  if ((rc = ensure_resident_v(t, "mfgp_plan_ivr"))) return rc;
+  const int64_t NH0 = t->NH, N0 = t->NL + t->NH;
+  if ((rc = ensure_cap(t, N0 + std::min<int64_t>(n_points, 32))) || (rc = ensure_v(t))) return rc;
+  // device state (the context's workspace serves the lattice step): mu, var, S, g, x [M] | tau's
+  // partials | vmax | vargmax | state {gate, count} | xn [2] | yn | cells, gains [P] | points [P][2] |
+  // cand | host weights | k_ivr_partial's partials | the covariance product's scratch | the
+  // saved resident posterior
+  const int64_t P = n_points, ntau = plan_tau_parts(M), nseg = ivr_segments(M);
+  WsLayout lay;
+  const size_t o_mu = lay.take(sizeof(double) * M), o_var = lay.take(sizeof(double) * M);
+  const size_t o_S = lay.take(sizeof(double) * M), o_g = lay.take(sizeof(double) * M);
+  const size_t o_x = lay.take(sizeof(double) * M), o_tau = lay.take(sizeof(double) * ntau);
+  const size_t o_misc = lay.take(sizeof(double) * 8);
+  const size_t o_cells = lay.take(sizeof(int64_t) * P), o_gains = lay.take(sizeof(double) * P);
+  const size_t o_pts = lay.take(sizeof(double) * 2 * P);
+  const size_t o_cand = lay.take(cand ? sizeof(int64_t) * nc : 0);
+  const size_t o_w = lay.take(w_host ? sizeof(double) * M : 0);
+  const size_t o_part = lay.take(sizeof(double) * (size_t)nseg * M);
+  const size_t o_work = lay.take(cov_work_bytes(t, N0 + P));
+  const size_t o_res = lay.take(sizeof(double) * plan_res_doubles(t));
+  char* ws = nullptr;
+  if (hipMalloc(&ws, lay.end) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: out of memory (%zu bytes of scratch)", lay.end);
+  }
+  auto at = [&](size_t o) { return reinterpret_cast<double*>(ws + o); };
+  double *mu_s = at(o_mu), *var_s = at(o_var), *S = at(o_S), *g = at(o_g), *x = at(o_x), *tau = at(o_tau);
+  double* vmax = at(o_misc);
+  int64_t* vargmax = reinterpret_cast<int64_t*>(vmax + 1);
+  int64_t* state = vargmax + 1;
+  double *xn = reinterpret_cast<double*>(state + 2), *yn = xn + 2;
+  int* gate = reinterpret_cast<int*>(state);
+  int64_t* dcells = reinterpret_cast<int64_t*>(ws + o_cells);
+  int64_t* dcand = cand ? reinterpret_cast<int64_t*>(ws + o_cand) : nullptr;
+  hipStream_t s = c->stream;
+  PlanSave sv;
+  bool entered = false;
+  auto fail = [&](int code) {
+    if (entered) (void)plan_leave(t, sv, true);
+    (void)hipStreamSynchronize(s);   // (the restore copies read ws)
+    (void)hipFree(ws);
+    return code;
+  };
+  if ((rc = plan_enter(t, sv, at(o_res)))) return fail(rc);
+  entered = true;
+  const double* dw = w;
+  if (w_host) {
+    if (hipMemcpyAsync(at(o_w), w, sizeof(double) * M, hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
+    dw = at(o_w);
+  }
+  const int64_t st0[2] = {1, 0};
+  if ((cand && hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      hipMemcpyAsync(state, st0, sizeof(st0), hipMemcpyHostToDevice, s) != hipSuccess)
+    return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
+  // the initial posterior, and S_0
+  if ((rc = batch_run(&t, 1, nullptr, nullptr, nullptr, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, false, true)))
+    return fail(rc);
+  auto numerators = [&]() -> int {
+    GPDesc d;
+    fill_desc(d, t);
+    HIP_TRY(launch_ivr_partial(d, nullptr, M, dw, 1, M, at(o_part), s));
+    HIP_TRY(launch_plan_ssum(at(o_part), (int)nseg, M, S, s));
+    return MFGP_OK;
+  };
+  if ((rc = numerators())) return fail(rc);
+  CovWork cw;
+  if ((rc = cov_work_init(t, ws + o_work, N0 + P, cw))) return fail(rc);
+  cw.a.x = x;
+  cw.a.S = S;
+  cw.a.g = g;
+  cw.a.tau_part = tau;
+  cw.a.ntau = (int)ntau;
+  cw.a.gate = gate;
+  PlanPick q{};
+  q.S = S;
+  q.var = var_s;
+  q.mu = mu_s;
+  q.grid = t->grid;
+  q.cand = dcand;
+  q.nc = nc;
+  q.noise = cw.a.h.noiseH;
+  q.jitter = cw.a.h.jitter;
+  q.min_gain = min_gain;
+  q.n_points = n_points;
+  q.state = state;
+  q.status = t->status;
+  q.xn = xn;
+  q.yn = yn;
+  q.cells = dcells;
+  q.gains = at(o_gains);
+  q.pts = at(o_pts);
+  t->gate_dev = gate;
+  int64_t done = 0;
+  bool active = true;
+  constexpr int64_t CH = 32;   // iterations per chunk
+  const int64_t one = 1;
+  while (active && done < n_points) {
+    int64_t C = std::min<int64_t>(CH, n_points - done);
+    if (refresh > 0) C = std::min<int64_t>(C, refresh - done % refresh);
+    const int64_t N = t->NL + t->NH;
+    if ((rc = ensure_cap(t, N + C)) || (rc = ensure_v(t))) return fail(rc);
+    if (!factor_current(t)) return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: factor lost on growth"));
+    q.status = t->status;
+    if (refresh > 0 && done > 0 && done % refresh == 0 && (rc = numerators())) return fail(rc);
+    for (int64_t it = 0; it < C; ++it) {
+      if (launch_ivr_pick(q, s) != hipSuccess) return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
+      if ((rc = batch_run(&t, 1, xn, yn, &one, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, true, true))) return fail(rc);
+      if (done + it + 1 >= n_points) break;   // the last pick: no score is read after it
+      const int64_t row = t->NL + t->NH - 1;
+      if (launch_plan_x(static_cast<const double*>(t->V), t->vld, row, M, dw, g, x, tau, gate, s) != hipSuccess)
+        return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
+      if ((rc = cov_work_run(t, cw, row + 1))) return fail(rc);
+    }
+    int64_t st[2] = {0, 0};
+    if (hipMemcpyAsync(st, state, sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: state read failed"));
+    active = (int)st[0] != 0;
+    const int64_t ran = st[1] - done;
+    done = st[1];
+    if (ran < C) {
+      // the loop stopped inside this chunk: drop the rows it did not append
+      if ((rc = mfgp_truncate(t, NH0 + done))) return fail(rc);
+    }
+    if ((rc = read_status(t))) return fail(rc);
+  }
+  if (done > 0 && (hipMemcpy(cells, dcells, sizeof(int64_t) * done, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(gains, q.gains, sizeof(double) * done, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(points, q.pts, sizeof(double) * 2 * done, hipMemcpyDefault) != hipSuccess))
+    return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: copy out failed"));
+  *count = done;
+  (void)plan_leave(t, sv);
+  const bool sync_ok = mfgp_ctx_synchronize(c) == MFGP_OK;   // (the posterior's restore copy reads ws)
+  (void)hipFree(ws);
+  return sync_ok ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: restore failed");
+}
+
 // Voronoi-cell reductions (simulator.py:194-323) on the device. Inputs may be
 // host or device memory (host ones are staged through the context workspace);
 // outputs likewise. Synchronous. field (host, [ncells]) or null: cell i reads

@@ -11,7 +11,7 @@
 using namespace mfgp;
 using namespace mfgp_host;
 
-extern "C" {
+namespace mfgp_host {
 
 // V holds all N rows of the current factor, hyperparameters and grid: the state
 // every predict path leaves (mfgp_cov_block reads rows [0, N) of it).
@@ -22,7 +22,7 @@ static bool v_covers(const mfgp_model* m) {
 // Bring V over all N rows, as mfgp_predict would (a pending or deferred append, new
 // hyperparameters, a new grid): into the model's result buffer, kept for the next
 // predict. `who`: the entry point, for the error message.
-static int ensure_resident_v(mfgp_model* m, const char* who) {
+int ensure_resident_v(mfgp_model* m, const char* who) {
   int rc;
   if (m->NL + m->NH == 0 || v_covers(m)) return MFGP_OK;
   if ((rc = ensure_spec_out(m))) return rc;
@@ -33,6 +33,83 @@ static int ensure_resident_v(mfgp_model* m, const char* who) {
                    (long long)m->v_n, (long long)(m->NL + m->NH));
   return MFGP_OK;
 }
+
+bool all_finite(const double* p, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+// K** x by the axis products: a lattice grid with both axes within KSS_AXIS_MAX
+static bool kss_separable(const mfgp_model* m) {
+  const GridLattice& L = m->lat;
+  return m->ctx->plan_sep && L.nx > 0 && L.ny > 0 && L.nx <= KSS_AXIS_MAX && L.ny <= KSS_AXIS_MAX &&
+         (int64_t)L.nx * L.ny == m->M;
+}
+
+// [part [segments][rows] | p [rows] | ax, ay | T [parts][M] | kx [M]]
+size_t cov_work_bytes(const mfgp_model* m, int64_t rows) {
+  WsLayout lay;
+  const int64_t r = std::max<int64_t>(rows, 1);
+  lay.take(sizeof(double) * (size_t)cov_segments(m->M) * r);
+  lay.take(sizeof(double) * (size_t)r);
+  if (kss_separable(m)) {
+    const size_t parts = m->kind == MFGP_SF ? 1 : 2;
+    lay.take(sizeof(double) * parts * ((size_t)m->lat.nx * m->lat.nx + (size_t)m->lat.ny * m->lat.ny));
+    lay.take(sizeof(double) * parts * (size_t)m->M);
+    lay.take(sizeof(double) * (size_t)m->M);
+  }
+  return lay.end;
+}
+
+int cov_work_init(mfgp_model* m, char* base, int64_t rows, CovWork& w) {
+  WsLayout lay;
+  const int64_t r = std::max<int64_t>(rows, 1);
+  w = CovWork{};
+  w.a.part = reinterpret_cast<double*>(base + lay.take(sizeof(double) * (size_t)cov_segments(m->M) * r));
+  w.a.pld = r;
+  w.a.p = reinterpret_cast<double*>(base + lay.take(sizeof(double) * (size_t)r));
+  w.a.M = m->M;
+  w.a.grid = m->grid;
+  w.a.h = derive_hyp(m->kind, m->hyp, m->jitter);
+  w.sep = kss_separable(m);
+  if (!w.sep) return MFGP_OK;
+  const GridLattice& L = m->lat;
+  KssArgs& k = w.k;
+  k.grid = m->grid;
+  k.nx = L.nx;
+  k.ny = L.ny;
+  k.sx = L.sx;
+  k.sy = L.sy;
+  k.parts = m->kind == MFGP_SF ? 1 : 2;
+  k.h = w.a.h;
+  const size_t nx2 = (size_t)L.nx * L.nx, ny2 = (size_t)L.ny * L.ny;
+  k.ax = reinterpret_cast<double*>(base + lay.take(sizeof(double) * k.parts * (nx2 + ny2)));
+  k.ay = k.ax + k.parts * nx2;
+  w.T = reinterpret_cast<double*>(base + lay.take(sizeof(double) * k.parts * (size_t)m->M));
+  w.kx = reinterpret_cast<double*>(base + lay.take(sizeof(double) * (size_t)m->M));
+  HIP_TRY(launch_kss_axes(k, m->ctx->stream));
+  return MFGP_OK;
+}
+
+int cov_work_run(mfgp_model* m, CovWork& w, int64_t n_rows) {
+  if (n_rows > w.a.pld) return set_err(MFGP_ERR_DEVICE, "covariance product: %lld rows exceed the scratch's %lld",
+                                       (long long)n_rows, (long long)w.a.pld);
+  w.a.V = static_cast<const double*>(m->V);
+  w.a.vld = m->vld;
+  w.a.N = n_rows;
+  w.a.kx = nullptr;
+  if (w.sep) {
+    HIP_TRY(launch_kss(w.k, w.a.x, w.T, w.kx, w.a.gate, m->ctx->stream));
+    w.a.kx = w.kx;
+  }
+  HIP_TRY(launch_cov_apply(w.a, m->ctx->stream));
+  return MFGP_OK;
+}
+
+}  // namespace mfgp_host
+
+extern "C" {
 
 int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t* cols, int64_t nb, double* out,
                    int64_t ldo, int flags) {
@@ -86,12 +163,6 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
 // LOOK_CHUNK points (one k_look_query launch each) unless the covariance is wanted,
 // whose GEMM reads every tile of one scratch.
 constexpr int64_t LOOK_CHUNK = 16384;
-
-static bool all_finite(const double* p, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
 
 // Integrated variance reduction per candidate cell (mfgp_ivr.hip): k_cov_block's GEMM
 // over the resident V with the column sums of w o cov^2 kept in registers.
@@ -170,6 +241,62 @@ int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const dou
   HIP_TRY(so.copy_back(nc, nw, c->stream));
   if (best) HIP_TRY(hipMemcpyAsync(best, dbest, sizeof(double) * nw, hipMemcpyDeviceToHost, c->stream));
   if (best_pos) HIP_TRY(hipMemcpyAsync(best_pos, dbp, sizeof(int64_t) * nw, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MFGP_OK;
+}
+
+// The posterior covariance applied to grid vectors (mfgp_plan_ivr.hip): per column two
+// streamed passes over the resident V and the K** x term, one column after another, so a
+// column's bits depend only on the model and that column.
+int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* out, int64_t ldo, int flags) {
+  const Entry entry(m);
+  int rc = entry.rc;
+  if (rc) return rc;
+  mfgp_ctx* c = m->ctx;
+  const int64_t M = m->M;
+  if (m->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
+  if (M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: the model has no grid (mfgp_set_grid)");
+  if (nx < 1 || nx > MFGP_IVR_MAXW)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: nx = %d is outside [1, %d]", nx, MFGP_IVR_MAXW);
+  if (!x || !out) return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: null vectors / output");
+  if (ldx < M)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: ldx = %lld is less than M = %lld", (long long)ldx, (long long)M);
+  if (ldo < M)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: ldo = %lld is less than M = %lld", (long long)ldo, (long long)M);
+  const bool x_host = !is_device_ptr(x);
+  for (int k = 0; x_host && k < nx; ++k)
+    if (!all_finite(x + (int64_t)k * ldx, M))
+      return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: the vectors must be finite (column %d)", k);
+  const bool prior = (flags & MFGP_COV_PRIOR) != 0;
+  if (!prior && (rc = ensure_resident_v(m, "mfgp_cov_apply"))) return rc;
+  const int64_t N = prior ? 0 : m->NL + m->NH;
+  // workspace: [host vectors [nx][M] | out, when it is host memory | the product's scratch]
+  const bool o_host = !is_device_ptr(out);
+  WsLayout lay;
+  const size_t o_x = lay.take(x_host ? sizeof(double) * (size_t)nx * M : 0);
+  const size_t o_out = lay.take(o_host ? sizeof(double) * (size_t)nx * M : 0);
+  const size_t o_work = lay.take(cov_work_bytes(m, N));
+  if ((rc = ensure_ws(c, lay.end))) return rc;
+  char* ws = reinterpret_cast<char*>(c->ws);
+  const double* dx = x;
+  int64_t dldx = ldx;
+  if (x_host) {
+    double* p = reinterpret_cast<double*>(ws + o_x);
+    HIP_TRY(hipMemcpy2DAsync(p, sizeof(double) * M, x, sizeof(double) * ldx, sizeof(double) * M, nx,
+                             hipMemcpyHostToDevice, c->stream));
+    dx = p;
+    dldx = M;
+  }
+  const StagedOut so(out, ldo, o_host, ws + o_out, M);
+  CovWork w;
+  if ((rc = cov_work_init(m, ws + o_work, N, w))) return rc;
+  for (int k = 0; k < nx; ++k) {
+    w.a.x = dx + (int64_t)k * dldx;
+    w.a.u = so.dev + (int64_t)k * so.ld;
+    if ((rc = cov_work_run(m, w, N))) return rc;
+  }
+  HIP_TRY(so.copy_back(M, nx, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return MFGP_OK;
 }

@@ -131,6 +131,26 @@ class DiagCov:
         src = self._live()
         return src.cov_block(self._cells(rows), self._cells(cols))
 
+    def apply(self, x):
+        """cov @ x without the matrix: x is [M] or [M, k] (k <= 8 columns), the result has the
+        same shape. Two streamed passes over the model's resident V per column
+        (_lib.Model.cov_apply), so it also serves grids whose dense covariance np.asarray
+        refuses -- e.g. w @ cov.apply(w), the variance of the field's mass over a region.
+        Stale once the model has moved on (RuntimeError), as the off-diagonal accessors;
+        not available on precision="f32" models (TypeError)."""
+        src = self._live()
+        if getattr(src, "dtype", _lib.F64) != _lib.F64:
+            raise TypeError("DiagCov.apply needs the fp64 resident V: not available on precision='f32' models")
+        xa = np.asarray(x, dtype=np.float64)
+        M = self.var.shape[0]
+        if xa.ndim not in (1, 2) or xa.shape[0] != M:
+            raise ValueError(f"x must be [M] or [M, k] with M = {M}")
+        if xa.ndim == 1:
+            return src.cov_apply(xa)
+        if xa.shape[1] == 0:
+            return np.empty((M, 0), dtype=np.float64)
+        return np.ascontiguousarray(src.cov_apply(np.ascontiguousarray(xa.T)).T)
+
     def __getitem__(self, idx):
         if isinstance(idx, tuple) and len(idx) == 2 and all(isinstance(i, (int, np.integer)) for i in idx):
             i, j = (int(v) % self.var.shape[0] for v in idx)

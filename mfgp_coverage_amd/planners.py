@@ -20,6 +20,11 @@ iteration is one decision launch for all of them and one batched 1-row append +
 predict (libmfgp_hip's mfgp_batch_sample_points, the lattice step where the batch
 takes it); each model stops at its own threshold.
 
+``compute_sample_points_ivr`` is the greedy planner on the integrated-variance
+criterion instead of the maximal variance (libmfgp_hip's mfgp_plan_ivr, DESIGN.md
+section 21): the same in-place loop, each pick scored by a rank-one update from one
+product of the posterior covariance with a grid vector.
+
 On any error (a step that is not positive definite raises LinAlgError, as updt /
 updt_hifi does inside the reference's loop) the models are as before the call, and
 the points are unspecified.
@@ -75,3 +80,27 @@ def compute_sample_points_batch(models, x_star, thresholds, console=False):
         if console:
             print("Sample points to reduce max var below " + str(thr[b]) + ": " + str(p.shape[0]))
     return pts
+
+
+def compute_sample_points_ivr(model, x_star, n_points, weights=None, candidates=None, min_gain=0.0, refresh=0):
+    """The greedy integrated-variance planner: up to ``n_points`` cells of ``x_star``, each
+    the allowed cell whose measurement lowers the weighted posterior variance of the
+    whole grid most given the picks before it (the A-optimal score of
+    ``variance_reduction``) -> ``(points [n, 2], gains [n])``,
+    ``gains[t]`` the score of pick t when it was chosen. ``weights``: None (ones) or [M];
+    ``candidates``: the allowed rows of ``x_star`` (None = all); the run stops before the
+    first pick whose score is below ``min_gain``; ``refresh = R > 0`` recomputes the scores'
+    numerators from scratch after every R picks. The model is unchanged, as after
+    ``compute_sample_points``; data, hyperparameters and grid reach the device the same way.
+    Not available on precision="f32" models (TypeError)."""
+    from . import _lib
+    if not isinstance(model, (SFGP, MFGP)):
+        raise TypeError("Invalid model type: must be SFGP or MFGP")
+    if model._dev().dtype != _lib.F64:
+        raise TypeError("compute_sample_points_ivr needs the fp64 resident V: not available on precision='f32' models")
+    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
+    model._sync_data()
+    model._push_hyp()
+    model._grid_to_device(xs)
+    _, pts, gains = model._dev().plan_ivr(n_points, weights, candidates, min_gain, refresh)
+    return pts, gains
