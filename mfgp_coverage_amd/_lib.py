@@ -180,6 +180,52 @@ def ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+# Argument helpers of the entry points below (no call into the library: tests/test_lib_args.py).
+
+def _addr(a):
+    """Pointer of an ndarray, non-null also for an empty one (an empty list or output is
+    still one); None for None."""
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def _handles(models):
+    """The models' handles as a C array, in order."""
+    return (ctypes.c_void_p * len(models))(*[m.handle.value for m in models])
+
+
+def _cells(v, M):
+    """A list of grid cells -> (int64 array, its pointer, its length); None = all M cells:
+    (None, None, M)."""
+    if v is None:
+        return None, None, M
+    a = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.int64)
+    return a, _addr(a), a.shape[0]
+
+
+def _dev_matrix(t, what, shape_text):
+    """A device tensor (data_ptr(), shape, stride(), dtype) [n] or [rows, n] of float64 with unit
+    column stride -> (address, rows, columns, leading dimension, 2-D?)."""
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) not in (1, 2) or \
+            (shape[-1] > 1 and stride[-1] != 1):
+        raise ValueError(f"{what} must be a float64 tensor {shape_text} with unit column stride")
+    two = len(shape) == 2
+    ld = int(stride[0]) if two and shape[0] > 1 else int(shape[-1])
+    return ctypes.c_void_p(int(t.data_ptr())), (int(shape[0]) if two else 1), int(shape[-1]), ld, two
+
+
+def _host_out(out, two, rows, min_cols, what):
+    """A caller's host output, float64 and writable with unit column stride: [>= rows, >= min_cols]
+    if two, else [>= min_cols] (taken as one row) -> (the [r, c] array over its memory, its leading
+    dimension). what: the text of the ValueError."""
+    if not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != (2 if two else 1) or \
+            out.strides[-1] != 8 or not out.flags.writeable or out.shape[-1] < min_cols or \
+            (two and (out.shape[0] < rows or out.strides[0] % 8)):
+        raise ValueError(what)
+    buf = out if two else out.reshape(1, -1)
+    return buf, (int(buf.strides[0] // 8) if buf.shape[0] > 1 else int(buf.shape[1]))
+
+
 class Context:
     """One HIP stream + workspace (mfgp_ctx)."""
 
@@ -424,33 +470,20 @@ class Model:
         Settles a pending append / new hyperparameters / a new grid as predict() would."""
         L = lib()
         M = L.mfgp_model_m(self.handle)
-
-        def lst(v):
-            if v is None:
-                return None, M
-            a = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.int64)
-            return a, a.shape[0]
-        r, na = lst(rows)
-        c, nb = lst(cols)
+        _r, rp, na = _cells(rows, M)
+        _c, cp, nb = _cells(cols, M)
         flags = COV_PRIOR if prior else 0
-
-        def ip(a):   # (an empty list is still a list: a non-null pointer)
-            return None if a is None else ctypes.c_void_p(a.ctypes.data)
         if isinstance(out, np.ndarray):
             # a caller's host matrix: row-major float64 rows, leading dimension = its row stride
-            if out.dtype != np.float64 or out.ndim != 2 or out.strides[1] != 8 or out.strides[0] % 8 or \
-                    out.shape[0] < na or not out.flags.writeable:
-                raise ValueError("out must be a writable row-major float64 matrix of at least [a] rows")
-            check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(out.ctypes.data),
-                                   int(out.strides[0] // 8 if ldo is None else ldo), flags))
-            return out[:na, :nb]
-        if out is not None:
-            check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(int(out)),
-                                   int(nb if ldo is None else ldo), flags))
-            return None
-        buf = np.empty((na, nb), dtype=np.float64)
-        check(L.mfgp_cov_block(self.handle, ip(r), na, ip(c), nb, ctypes.c_void_p(buf.ctypes.data), nb, flags))
-        return buf
+            _host_out(out, True, na, 0, "out must be a writable row-major float64 matrix of at least [a] rows")
+            res, o_p, ld = out[:na, :nb], _addr(out), out.strides[0] // 8
+        elif out is not None:
+            res, o_p, ld = None, ctypes.c_void_p(int(out)), nb
+        else:
+            res = np.empty((na, nb), dtype=np.float64)
+            o_p, ld, ldo = _addr(res), nb, None
+        check(L.mfgp_cov_block(self.handle, rp, na, cp, nb, o_p, int(ld if ldo is None else ldo), flags))
+        return res
 
     def var_reduction(self, cand=None, weights=None, out=None, with_best=False):
         """Integrated variance reduction per candidate cell (mfgp_var_reduction): how much the
@@ -467,24 +500,11 @@ class Model:
         only on the model, its cell and its weight vector."""
         L = lib()
         M = L.mfgp_model_m(self.handle)
-        if cand is None:
-            cp, nc = None, M
-        else:
-            ca = np.ascontiguousarray(np.asarray(cand).reshape(-1), dtype=np.int64)
-            cp, nc = ctypes.c_void_p(ca.ctypes.data), ca.shape[0]
-
-        def dev2(t, what):   # a device tensor: (address, rows, columns, leading dimension, 2-D?)
-            shape, stride = tuple(t.shape), tuple(t.stride())
-            if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) not in (1, 2) or \
-                    (shape[-1] > 1 and stride[-1] != 1):
-                raise ValueError(f"{what} must be a float64 tensor [n] or [nw, n] with unit column stride")
-            two = len(shape) == 2
-            ld = int(stride[0]) if two and shape[0] > 1 else int(shape[-1])
-            return ctypes.c_void_p(int(t.data_ptr())), (int(shape[0]) if two else 1), int(shape[-1]), ld, two
+        _ca, cp, nc = _cells(cand, M)
         if weights is None:
             wp, nw, ldw, two = None, 1, M, False
         elif hasattr(weights, "data_ptr"):
-            wp, nw, wn, ldw, two = dev2(weights, "weights")
+            wp, nw, wn, ldw, two = _dev_matrix(weights, "weights", "[n] or [nw, n]")
             if wn < M:
                 raise ValueError(f"weights must have at least M = {M} columns")
         else:
@@ -493,30 +513,20 @@ class Model:
                 raise ValueError(f"weights must be [M] or [nw, >= M] with M = {M}")
             two = wa.ndim == 2
             wa = np.ascontiguousarray(wa.reshape(-1, wa.shape[-1]))
-            wp, nw, ldw = ctypes.c_void_p(wa.ctypes.data), wa.shape[0], wa.shape[1]
+            wp, nw, ldw = _addr(wa), wa.shape[0], wa.shape[1]
         bv = np.empty(max(nw, 1), dtype=np.float64) if with_best else None
         bp = np.empty(max(nw, 1), dtype=np.int64) if with_best else None
-
-        def op(a):
-            return None if a is None else ctypes.c_void_p(a.ctypes.data)
         if out is not None and hasattr(out, "data_ptr"):
-            o_p, orows, ocols, ldo, otwo = dev2(out, "out")
+            o_p, orows, ocols, ldo, otwo = _dev_matrix(out, "out", "[n] or [nw, n]")
             if otwo != two or orows < nw:
                 raise ValueError("out must have the shape of the result")
             res = None
         else:
-            if out is None:
-                buf = np.empty((nw, nc), dtype=np.float64)
-            else:
-                if not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != (2 if two else 1) or \
-                        out.strides[-1] != 8 or not out.flags.writeable or (two and (out.shape[0] < nw or
-                                                                                       out.strides[0] % 8)):
-                    raise ValueError("out must be a writable float64 array of the result's shape")
-                buf = out if two else out.reshape(1, -1)
-            ldo = int(buf.strides[0] // 8) if buf.shape[0] > 1 else int(buf.shape[1])
-            o_p = ctypes.c_void_p(buf.ctypes.data)
+            buf, ldo = (np.empty((nw, nc), dtype=np.float64), nc) if out is None else \
+                _host_out(out, two, nw, 0, "out must be a writable float64 array of the result's shape")
+            o_p = _addr(buf)
             res = buf[:nw, :nc] if two else buf[0, :nc]
-        check(L.mfgp_var_reduction(self.handle, cp, nc, wp, nw, ldw, o_p, ldo, op(bv), op(bp)))
+        check(L.mfgp_var_reduction(self.handle, cp, nc, wp, nw, ldw, o_p, ldo, _addr(bv), _addr(bp)))
         if not with_best:
             return res
         if two:
@@ -533,43 +543,27 @@ class Model:
         and leaves it unchanged; a row's bits depend only on the model and that row of x."""
         L = lib()
         M = L.mfgp_model_m(self.handle)
-
-        def dev2(t, what):
-            shape, stride = tuple(t.shape), tuple(t.stride())
-            if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) not in (1, 2) or \
-                    (shape[-1] > 1 and stride[-1] != 1):
-                raise ValueError(f"{what} must be a float64 tensor [M] or [k, M] with unit column stride")
-            two = len(shape) == 2
-            ld = int(stride[0]) if two and shape[0] > 1 else int(shape[-1])
-            return ctypes.c_void_p(int(t.data_ptr())), (int(shape[0]) if two else 1), int(shape[-1]), ld, two
         if hasattr(x, "data_ptr"):
-            xp, nx, xn, ldx, two = dev2(x, "x")
+            xp, nx, xn, ldx, two = _dev_matrix(x, "x", "[M] or [k, M]")
         else:
             xa = np.asarray(x, dtype=np.float64)
             if xa.ndim not in (1, 2):
                 raise ValueError(f"x must be [M] or [k, M] with M = {M}")
             two = xa.ndim == 2
             xa = np.ascontiguousarray(xa.reshape(-1, xa.shape[-1]))
-            xp, nx, xn, ldx = ctypes.c_void_p(xa.ctypes.data), xa.shape[0], xa.shape[1], xa.shape[1]
+            xp, nx, xn, ldx = _addr(xa), xa.shape[0], xa.shape[1], xa.shape[1]
         if xn != M:
             raise ValueError(f"x must have M = {M} columns (got {xn})")
         flags = COV_PRIOR if prior else 0
         if out is not None and hasattr(out, "data_ptr"):
-            o_p, orows, ocols, ldo, otwo = dev2(out, "out")
+            o_p, orows, ocols, ldo, otwo = _dev_matrix(out, "out", "[M] or [k, M]")
             if otwo != two or orows < nx or ocols < M:
                 raise ValueError("out must have the shape of x")
             check(L.mfgp_cov_apply(self.handle, xp, nx, ldx, o_p, ldo, flags))
             return None
-        if out is None:
-            buf = np.empty((nx, M), dtype=np.float64)
-        else:
-            if not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != (2 if two else 1) or \
-                    out.strides[-1] != 8 or not out.flags.writeable or out.shape[-1] < M or \
-                    (two and (out.shape[0] < nx or out.strides[0] % 8)):
-                raise ValueError("out must be a writable float64 array of x's shape")
-            buf = out if two else out.reshape(1, -1)
-        ldo = int(buf.strides[0] // 8) if buf.shape[0] > 1 else int(buf.shape[1])
-        check(L.mfgp_cov_apply(self.handle, xp, nx, ldx, ctypes.c_void_p(buf.ctypes.data), ldo, flags))
+        buf, ldo = (np.empty((nx, M), dtype=np.float64), M) if out is None else \
+            _host_out(out, two, nx, M, "out must be a writable float64 array of x's shape")
+        check(L.mfgp_cov_apply(self.handle, xp, nx, ldx, _addr(buf), ldo, flags))
         return buf[:nx, :M] if two else buf[0, :M]
 
     def plan_ivr(self, n_points, weights=None, cand=None, min_gain=0.0, refresh=0):
@@ -583,11 +577,7 @@ class Model:
         L = lib()
         M = L.mfgp_model_m(self.handle)
         n_points = int(n_points)
-        if cand is None:
-            cp, nc = None, M
-        else:
-            ca = np.ascontiguousarray(np.asarray(cand).reshape(-1), dtype=np.int64)
-            cp, nc = ctypes.c_void_p(ca.ctypes.data), ca.shape[0]
+        _ca, cp, nc = _cells(cand, M)
         if weights is None:
             wp, ldw = None, M
         elif hasattr(weights, "data_ptr"):
@@ -600,15 +590,14 @@ class Model:
             wa = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
             if wa.ndim != 1:
                 raise ValueError(f"weights must be [>= M] with M = {M}: one weight vector")
-            wp, ldw = ctypes.c_void_p(wa.ctypes.data), wa.shape[0]
+            wp, ldw = _addr(wa), wa.shape[0]
         P = max(n_points, 1)
         cells = np.empty(P, dtype=np.int64)
         pts = np.empty((P, 2), dtype=np.float64)
         gains = np.empty(P, dtype=np.float64)
         n = ctypes.c_int64(0)
         check(L.mfgp_plan_ivr(self.handle, wp, ldw, cp, nc, n_points, float(min_gain), int(refresh),
-                              ctypes.c_void_p(cells.ctypes.data), ctypes.c_void_p(pts.ctypes.data),
-                              ctypes.c_void_p(gains.ctypes.data), ctypes.byref(n)))
+                              _addr(cells), _addr(pts), _addr(gains), ctypes.byref(n)))
         k = int(n.value)
         return cells[:k].copy(), pts[:k].copy(), gains[:k].copy()
 
@@ -631,14 +620,15 @@ class Model:
         o_v0 = np.empty(n, dtype=np.float64) if var0 else None
         o_v = np.empty(n, dtype=np.float64) if var else None
         o_c = np.empty((n, max(ldc, 1)), dtype=np.float64) if cov else None
-
-        def op(a):   # (an empty output is still asked for: a non-null pointer)
-            return None if a is None else ctypes.c_void_p(a.ctypes.data)
-        check(lib().mfgp_query(self.handle, op(Xq), n, op(XL), XL.shape[0], op(XH), XH.shape[0],
-                               op(o_mu), op(o_v0), op(o_v), op(o_c), ldc))
+        check(lib().mfgp_query(self.handle, _addr(Xq), n, _addr(XL), XL.shape[0], _addr(XH), XH.shape[0],
+                               _addr(o_mu), _addr(o_v0), _addr(o_v), _addr(o_c), ldc))
         return QueryResult(o_mu, o_v0, o_v, None if o_c is None else o_c[:, :n])
 
     SAMPLE_DIMS = ("nz", "M", "N", "fields", "rx0", "ry0", "rx1", "ry1")
+    STATS_KEYS = ("factor_rows", "v_rows", "full_factor", "inc_factor", "full_predict", "vstream",
+                  "lattice_nx", "lattice_ny", "lattice", "lattice_virtual", "lattice_arg", "lattice_g2",
+                  "post_copy", "early_pd", "look_border", "look_query", "sample_solve", "sample_gemm",
+                  "lattice_vcol", "vcol_rows_built")
 
     def sample_dims(self, prior=False):
         """{nz, M, N, fields, rx0, ry0, rx1, ry1} of sample() (mfgp_sample_dims): nz normals
@@ -672,21 +662,17 @@ class Model:
             if S > z.shape[0]:
                 raise ValueError("S exceeds the rows of normals")
             ldz = (z.strides[0] // 8 if z.shape[0] > 1 else z.shape[1]) if ldz is None else int(ldz)
-            zp = ctypes.c_void_p(z.ctypes.data)
+            zp = _addr(z)
         if isinstance(out, np.ndarray):
-            if out.dtype != np.float64 or out.ndim != 2 or out.strides[1] != 8 or out.strides[0] % 8 or \
-                    out.shape[0] < S or not out.flags.writeable:
-                raise ValueError("out must be a writable row-major float64 matrix of at least [S] rows")
-            ld = (out.strides[0] // 8 if out.shape[0] > 1 else out.shape[1]) if ldo is None else int(ldo)
-            check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(out.ctypes.data), ld, flags))
-            return out[:S, :M]
-        if out is not None:
-            check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(int(out)),
-                                          int(M if ldo is None else ldo), flags))
-            return None
-        buf = np.empty((S, max(M, 1)), dtype=np.float64)
-        check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, ctypes.c_void_p(buf.ctypes.data), max(M, 1), flags))
-        return buf[:, :M]
+            _, ld = _host_out(out, True, S, 0, "out must be a writable row-major float64 matrix of at least [S] rows")
+            res, o_p = out[:S, :M], _addr(out)
+        elif out is not None:
+            res, o_p, ld = None, ctypes.c_void_p(int(out)), M
+        else:
+            buf = np.empty((S, max(M, 1)), dtype=np.float64)
+            res, o_p, ld, ldo = buf[:, :M], _addr(buf), max(M, 1), None
+        check(L.mfgp_sample_posterior(self.handle, zp, S, ldz, o_p, int(ld if ldo is None else ldo), flags))
+        return res
 
     def serial(self):
         """The model's posterior serial (mfgp_model_serial): changes whenever its rows,
@@ -722,13 +708,9 @@ class Model:
         {sample_solve, sample_gemm}: the k_sample_solve / k_sample_gemm launches of sample();
         {lattice_vcol}: the lattice steps whose w units read the column store of V;
         {vcol_rows_built}: the rows its catch-up (k_vcol_build) transposed into it."""
-        out = (ctypes.c_int64 * 20)()
-        check(lib().mfgp_model_stats(self.handle, out, 20))
-        keys = ("factor_rows", "v_rows", "full_factor", "inc_factor", "full_predict", "vstream",
-                "lattice_nx", "lattice_ny", "lattice", "lattice_virtual", "lattice_arg", "lattice_g2",
-                "post_copy", "early_pd", "look_border", "look_query", "sample_solve", "sample_gemm",
-                "lattice_vcol", "vcol_rows_built")
-        return dict(zip(keys, (int(v) for v in out)))
+        out = (ctypes.c_int64 * len(self.STATS_KEYS))()
+        check(lib().mfgp_model_stats(self.handle, out, len(self.STATS_KEYS)))
+        return dict(zip(self.STATS_KEYS, (int(v) for v in out)))
 
     def debug_read_v(self):
         """Tests only: (V [n, M], Vc [M, n] or None, the store's valid rows): the resident V's
@@ -818,21 +800,10 @@ def batch_append_predict(models, X, y, k, mu_ptr, var_ptr, asynchronous=False, v
     X, y: integer device (or host) addresses of the concatenated new rows;
     k: per-model row counts; mu_ptr/var_ptr: device addresses of [sum M] outputs;
     vmax_ptr / vargmax_ptr: optional device addresses of [n] float64 / int64 outputs
-    (fused np.amax / np.argmax of each model's variance).
+    (fused np.amax / np.argmax of each model's variance; without them the _ex entry point
+    is mfgp_batch_append_predict itself).
     """
-    n = len(models)
-    arr = (ctypes.c_void_p * n)(*[m.handle.value for m in models])
-    ks = (ctypes.c_int64 * n)(*[int(v) for v in k])
-    if vmax_ptr is None and vargmax_ptr is None:
-        rc = lib().mfgp_batch_append_predict(arr, n, ctypes.c_void_p(X), ctypes.c_void_p(y), ks,
-                                             ctypes.c_void_p(mu_ptr), ctypes.c_void_p(var_ptr),
-                                             ASYNC if asynchronous else 0)
-    else:
-        rc = lib().mfgp_batch_append_predict_ex(arr, n, ctypes.c_void_p(X), ctypes.c_void_p(y), ks,
-                                                ctypes.c_void_p(mu_ptr), ctypes.c_void_p(var_ptr),
-                                                ctypes.c_void_p(vmax_ptr), ctypes.c_void_p(vargmax_ptr),
-                                                ASYNC if asynchronous else 0)
-    check(rc)
+    Batch(models, k).append_predict(X, y, mu_ptr, var_ptr, asynchronous, vmax_ptr, vargmax_ptr)
 
 
 class Batch:
@@ -841,10 +812,9 @@ class Batch:
 
     def __init__(self, models, k):
         self.models = list(models)
-        n = len(self.models)
-        self.n = n
-        self.arr = (ctypes.c_void_p * n)(*[m.handle.value for m in self.models])
-        self.ks = (ctypes.c_int64 * n)(*[int(v) for v in k])
+        self.n = len(self.models)
+        self.arr = _handles(self.models)
+        self.ks = (ctypes.c_int64 * self.n)(*[int(v) for v in k])
 
     def truncate(self, n_keep_hifi):
         check(lib().mfgp_batch_truncate(self.arr, self.n, int(n_keep_hifi)))
@@ -858,10 +828,8 @@ class Batch:
 
 def batch_append_factor(models, X, y, k, asynchronous=False):
     """Append + refactor a batch (device or host row pointers); no predict."""
-    n = len(models)
-    arr = (ctypes.c_void_p * n)(*[m.handle.value for m in models])
-    ks = (ctypes.c_int64 * n)(*[int(v) for v in k])
-    check(lib().mfgp_batch_append_factor(arr, n, ctypes.c_void_p(X), ctypes.c_void_p(y), ks,
+    b = Batch(models, k)
+    check(lib().mfgp_batch_append_factor(b.arr, b.n, ctypes.c_void_p(X), ctypes.c_void_p(y), b.ks,
                                          ASYNC if asynchronous else 0))
 
 
@@ -869,20 +837,17 @@ def batch_sample_points(models, thresholds, max_points):
     """mfgp_batch_sample_points: compute_sample_points (simulator.py:326-374) for every
     model of the batch, stepped together -> one [n_b, 2] array of chosen cells per model."""
     n = len(models)
-    arr = (ctypes.c_void_p * n)(*[m.handle.value for m in models])
     thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (n,)))
     P = max(int(max_points), 1)
     pts = np.empty((n, P, 2), dtype=np.float64)
     cnt = np.zeros(n, dtype=np.int64)
-    check(lib().mfgp_batch_sample_points(arr, n, ptr(thr), int(max_points), ptr(pts), ptr(cnt)))
+    check(lib().mfgp_batch_sample_points(_handles(models), n, ptr(thr), int(max_points), ptr(pts), ptr(cnt)))
     return [pts[b, :cnt[b]].copy() for b in range(n)]
 
 
 def batch_predict(models, mu_ptr, var_ptr, asynchronous=False):
     """Posterior mean / variance of a batch from its current factors."""
-    n = len(models)
-    arr = (ctypes.c_void_p * n)(*[m.handle.value for m in models])
-    check(lib().mfgp_batch_predict(arr, n, ctypes.c_void_p(mu_ptr), ctypes.c_void_p(var_ptr),
+    check(lib().mfgp_batch_predict(_handles(models), len(models), ctypes.c_void_p(mu_ptr), ctypes.c_void_p(var_ptr),
                                    ASYNC if asynchronous else 0))
 
 

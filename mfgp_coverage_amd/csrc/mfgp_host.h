@@ -4,13 +4,16 @@
 //
 //   mfgp_capi.hip      contexts, models, their state helpers, set / append / predict, stats
 //   mfgp_step.hip      the step engine: enqueue_*, batch_run, the batch entry points
-//   mfgp_planners.hip  the sample-point loops and the cell reductions
+//   mfgp_planners.hip  the planner loops (sample points, batched, integrated variance) on
+//                      one scaffold (PlanRun), and the cell reductions
 //   mfgp_resident.hip  consumers of the resident V and factor: covariance blocks,
-//                      variance reduction, look-ahead queries, pathwise samples
+//                      variance reduction, look-ahead queries, pathwise samples; their
+//                      shared argument checks (need_f64_grid, check_cells, finite_rows)
 //   mfgp_train.hip     NLML and its gradient, single and batched
 //
 // The shared helpers live in mfgp_host, a namespace of hidden visibility: they link
-// across the library's objects and add nothing to its dynamic symbol table.
+// across the library's objects and add nothing to its dynamic symbol table. Matrices the
+// caller may hold in host memory pass through StagedIn (inputs) and StagedOut (outputs).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -412,6 +415,24 @@ struct StagedOut {
   }
 };
 
+// The input-side twin: a matrix [rows][cols] with leading dimension ldp that the kernels
+// read at `dev` with leading dimension `ld` -- in place when it is device memory, else from
+// the packed image at `stage` (workspace) that upload enqueues.
+struct StagedIn {
+  const double* dev;
+  int64_t ld;
+  const double* user;   // the host matrix upload copies (null: nothing to copy)
+  int64_t user_ld, rows;
+  StagedIn(const double* p, int64_t rows, int64_t cols, int64_t ldp, bool host, void* stage)
+      : dev(host ? static_cast<const double*>(stage) : p), ld(host ? cols : ldp), user(host ? p : nullptr), user_ld(ldp),
+        rows(rows) {}
+  hipError_t upload(hipStream_t s) const {
+    if (!user) return hipSuccess;
+    return hipMemcpy2DAsync(const_cast<double*>(dev), sizeof(double) * ld, user, sizeof(double) * user_ld,
+                            sizeof(double) * ld, rows, hipMemcpyHostToDevice, s);
+  }
+};
+
 // table width of the lattice step: 64, 128, 192 or 256 where the step applies (lat_eligible:
 // <= NT). At 192 zq rounds down to 2 and a Z unit's second thread group is a partial one
 // (lat_zunit); every width, rectangles and a degenerate axis: tests/test_gpu_lattice_grids.py
@@ -463,6 +484,14 @@ int batch_run(mfgp_model** models, int count, const double* X, const double* y, 
 // mfgp_resident.hip
 bool all_finite(const double* p, int64_t n);
 int ensure_resident_v(mfgp_model* m, const char* who);
+// The argument checks the consumers of the resident V share (`who`: the entry point, for
+// the message). need_f64_grid: an fp64 model with a grid. check_cells: a NULL list stands
+// for all M cells and n must say so; the entries of any other lie in [0, M).
+// finite_rows: the first of p's rows ([rows][cols], leading dimension ld) with a
+// non-finite entry, or -1.
+int need_f64_grid(const mfgp_model* m, const char* who);
+int check_cells(const char* who, const char* name, const int64_t* list, int64_t n, int64_t M);
+int64_t finite_rows(const double* p, int64_t rows, int64_t ld, int64_t cols);
 // The scratch and the fixed arguments of covariance products u = K** x - V^T (V x) on
 // m's grid (mfgp_plan_ivr.hip): laid out at `base` (cov_work_bytes(m, rows) bytes, 256-byte
 // aligned, for a V of at most `rows` rows). cov_work_init enqueues the axis Gram matrices

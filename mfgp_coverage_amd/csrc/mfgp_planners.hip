@@ -1,6 +1,8 @@
-// The planners of libmfgp_hip.so: the sample-point loops (mfgp_sample_points,
-// mfgp_batch_sample_points) over the batch step, and the host side of the Voronoi-cell
-// reductions (mfgp_cells.hip).
+// The planners of libmfgp_hip.so: the three loops that run on the caller's model in
+// place -- the sample-point loops (mfgp_sample_points, mfgp_batch_sample_points) and the
+// greedy integrated-variance planner (mfgp_plan_ivr), all over the batch step and on one
+// scaffold (PlanRun: enter, grow, chunk_end, finish, and fail on every error path) -- and
+// the host side of the Voronoi-cell reductions (mfgp_cells.hip).
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -9,8 +11,6 @@
 
 using namespace mfgp;
 using namespace mfgp_host;
-
-extern "C" {
 
 // The planners work on the caller's model itself instead of a deep copy (sim:339):
 // the rows they append lie past the model's own, and the factor, z, V, F and the
@@ -127,6 +127,111 @@ static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   return MFGP_OK;
 }
 
+// Before a loop: earlier ASYNC steps' verdicts first (the loop's decisions read the
+// status words), then every model's factor.
+static int plan_ready(mfgp_ctx* c, mfgp_model* const* t, int count) {
+  int rc;
+  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
+  for (int b = 0; b < count; ++b)
+    if ((rc = update_factor(t[b]))) return rc;
+  return MFGP_OK;
+}
+
+// What the three loops share: the models a loop runs on in place, what plan_enter saved
+// of each, the loop's device scratch and its state words, and the steps every loop takes
+// the same way. An entry point checks its arguments, lays the scratch out (WsLayout),
+// enqueues its iterations in chunks of PLAN_CHUNK behind the device gates and copies its
+// results out; from `enter` on, every error returns through `fail`, which leaves the
+// models as they were before the call.
+constexpr int64_t PLAN_CHUNK = 32;   // iterations enqueued per host synchronisation
+struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no symbols of the library)
+  const char* who;            // the entry point, for the messages
+  mfgp_ctx* c;
+  mfgp_model* const* t;       // the models
+  int count;
+  std::vector<PlanSave> sv;
+  int entered = 0;            // the models plan_enter has saved
+  char* ws = nullptr;         // the scratch: the run's own (`own`) or the context's workspace
+  bool owned = false;
+  int64_t* state = nullptr;   // device [count][2]: {gate, rows appended}
+  std::vector<int64_t> st;    // its host image: {1, 0} each for `open`, then as of the last chunk_end
+  std::vector<int> live;      // the models whose status chunk_end reads (the batched loop prunes it)
+  int64_t done = 0;           // a single-model loop: the rows appended so far
+
+  PlanRun(const char* who_, mfgp_ctx* c_, mfgp_model* const* t_, int n)
+      : who(who_), c(c_), t(t_), count(n), sv(n), st(2 * (size_t)n, 0), live(n) {
+    for (int b = 0; b < n; ++b) {
+      st[2 * b] = 1;
+      live[b] = b;
+    }
+  }
+  template <class T = double>
+  T* at(size_t o) const {
+    return reinterpret_cast<T*>(ws + o);
+  }
+  bool own(size_t bytes) {
+    owned = hipMalloc(&ws, bytes) == hipSuccess;
+    if (!owned) (void)hipGetLastError();
+    return owned;
+  }
+  // plan_enter for each model; `room`: the models' plan_res_doubles, one after another
+  int enter(double* room) {
+    for (; entered < count; room += plan_res_doubles(t[entered]), ++entered)
+      if (const int rc = plan_enter(t[entered], sv[entered], room)) return rc;
+    return MFGP_OK;
+  }
+  // an error after enter: the models restored, the scratch released; returns code
+  int fail(int code) {
+    for (int b = 0; b < entered; ++b) (void)plan_leave(t[b], sv[b], true);
+    (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
+    if (owned) (void)hipFree(ws);
+    return code;
+  }
+  // the gates opened, the counts zeroed
+  hipError_t open() {
+    return hipMemcpyAsync(state, st.data(), sizeof(int64_t) * st.size(), hipMemcpyHostToDevice, c->stream);
+  }
+  // room for C more rows of m, with its factor and V kept
+  int grow(mfgp_model* m, int64_t C) {
+    int rc;
+    if ((rc = ensure_cap(m, m->NL + m->NH + C)) || (rc = ensure_v(m))) return rc;
+    if (!factor_current(m)) return set_err(MFGP_ERR_DEVICE, "%s: factor lost on growth", who);
+    return MFGP_OK;
+  }
+  // A chunk's end: the state words read back and the stream drained, then the live
+  // models' status words. C >= 0, a single-model loop's chunk of C iterations: `done`
+  // follows, and if the loop stopped inside the chunk, the rows it did not append go.
+  int chunk_end(int64_t C = -1) {
+    int rc;
+    if (hipMemcpyAsync(st.data(), state, sizeof(int64_t) * st.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+      return set_err(MFGP_ERR_DEVICE, "%s: state read failed", who);
+    if (C >= 0) {
+      const int64_t ran = st[1] - done;
+      done = st[1];
+      if (ran < C && (rc = mfgp_truncate(t[0], sv[0].NH0 + done))) return rc;
+    }
+    for (int b : live)
+      if ((rc = read_status(t[b]))) return rc;
+    return MFGP_OK;
+  }
+  // The loop's end: the models back to their own rows and state, the last wait (the
+  // restore copies read ws: the context's, with its deferred verdicts, or the stream's
+  // alone), the scratch released. Returns the first failure of the restores and the wait.
+  int finish(bool ctx_sync) {
+    int rc = MFGP_OK;
+    for (int b = 0; b < entered; ++b)
+      if (const int r = plan_leave(t[b], sv[b]); r && !rc) rc = r;
+    entered = 0;
+    const int sync = ctx_sync ? mfgp_ctx_synchronize(c)
+                              : (hipStreamSynchronize(c->stream) == hipSuccess ? MFGP_OK : MFGP_ERR_DEVICE);
+    if (owned) (void)hipFree(ws);
+    return rc ? rc : sync;
+  }
+};
+
+extern "C" {
+
 // compute_sample_points (simulator.py:326-374) as a device loop. Each iteration
 // is k_choi_select (argmax cell + its mean -> new hifi row, or stop), a 1-row
 // bordered append and a one-pass predict with the fused argmax, all gated by a
@@ -143,53 +248,40 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
   *count = 0;
   mfgp_ctx* c = model->ctx;
   if (!c->incremental) return set_err(MFGP_ERR_ARG, "mfgp_sample_points needs incremental updates enabled");
-  // earlier ASYNC steps' verdicts first: the loop's decisions read the status word
-  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
-  if ((rc = update_factor(model))) return rc;
   // the reference works on a deep copy (sim:339); here on the model itself, brought
   // back to its own rows and state at the end (plan_enter / plan_leave)
   mfgp_model* t = model;
+  if ((rc = plan_ready(c, &t, 1))) return rc;
   const int64_t M = t->M;
-  // workspace: mu, var [M] | vmax | vargmax | state {gate, count} | points [max_points][2] |
+  // the context's workspace: mu, var [M] | vmax, vargmax, state {gate, count} | points [max_points][2] |
   // the saved resident posterior
-  const size_t npt = 2 * (size_t)std::max<int64_t>(max_points, 1);
-  const size_t nd = 2 * (size_t)M + 4 + npt + plan_res_doubles(t);
-  if ((rc = ensure_ws(c, sizeof(double) * nd))) return rc;
-  double* mu_s = c->ws;
-  double* var_s = mu_s + M;
-  double* vmax = var_s + M;
+  WsLayout lay;
+  const size_t o_mu = lay.take(sizeof(double) * M), o_var = lay.take(sizeof(double) * M);
+  const size_t o_misc = lay.take(sizeof(double) * 4);
+  const size_t o_pts = lay.take(sizeof(double) * 2 * (size_t)std::max<int64_t>(max_points, 1));
+  const size_t o_res = lay.take(sizeof(double) * plan_res_doubles(t));
+  if ((rc = ensure_ws(c, lay.end))) return rc;
+  PlanRun run("sample_points", c, &t, 1);
+  run.ws = reinterpret_cast<char*>(c->ws);
+  double *mu_s = run.at(o_mu), *var_s = run.at(o_var), *vmax = run.at(o_misc), *pts = run.at(o_pts);
   int64_t* vargmax = reinterpret_cast<int64_t*>(vmax + 1);
-  int64_t* state = vargmax + 1;
-  double* pts = reinterpret_cast<double*>(state + 2);
-  int* gate = reinterpret_cast<int*>(state);
-  PlanSave sv;
-  if ((rc = plan_enter(t, sv, pts + npt))) return rc;
-  auto fail = [&](int code) {
-    (void)plan_leave(t, sv, true);
-    (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
-    return code;
-  };
+  run.state = vargmax + 1;
+  int* gate = reinterpret_cast<int*>(run.state);
+  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
   // initial posterior (sim:340-342)
-  if ((rc = batch_run(&t, 1, nullptr, nullptr, nullptr, mu_s, var_s, vmax, vargmax, 0, false, true))) return fail(rc);
-  const int64_t st0[2] = {1, 0};
-  if (hipMemcpyAsync(state, st0, sizeof(st0), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return fail(set_err(MFGP_ERR_DEVICE, "state upload failed"));
-  const int64_t NH0 = t->NH;
-  int64_t done = 0;
+  if ((rc = batch_run(&t, 1, nullptr, nullptr, nullptr, mu_s, var_s, vmax, vargmax, 0, false, true))) return run.fail(rc);
+  if (run.open() != hipSuccess) return run.fail(set_err(MFGP_ERR_DEVICE, "state upload failed"));
   bool active = true;
-  constexpr int64_t CH = 32;   // iterations per chunk (two descriptors each)
-  while (active && done < max_points) {
-    const int64_t C = std::min<int64_t>(CH, max_points - done);
-    const int64_t N = t->NL + t->NH;
-    if ((rc = ensure_cap(t, N + C)) || (rc = ensure_v(t))) return fail(rc);
-    if (!factor_current(t)) return fail(set_err(MFGP_ERR_DEVICE, "sample_points: factor lost on growth"));
+  while (active && run.done < max_points) {
+    const int64_t C = std::min<int64_t>(PLAN_CHUNK, max_points - run.done);   // (two descriptors each)
+    if ((rc = run.grow(t, C))) return run.fail(rc);
     int slot;
     GPDesc* hd = acquire_slot(c, slot, rc);
-    if (!hd) return fail(rc);
+    if (!hd) return run.fail(rc);
     for (int64_t it = 0; it < C; ++it) {
-      t->NH += 1;   // assume the iteration runs; truncated below if the loop stopped
+      t->NH += 1;   // assume the iteration runs; truncated at the chunk's end if the loop stopped
       GPDesc& fd = hd[2 * it];
-      if ((rc = fill_inc_desc(fd, t))) return fail(rc);
+      if ((rc = fill_inc_desc(fd, t))) return run.fail(rc);
       fd.mu = mu_s;
       fd.vmax = vmax;
       fd.vargmax = vargmax;
@@ -212,7 +304,7 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
     set_rsplit(c, hd + 1, 1);
     for (int64_t i = 0; i < 2 * C; ++i) hd[i].rsplit = hd[1].rsplit;
     const GPDesc* dd = nullptr;
-    if ((rc = upload_slot(c, slot, (int)(2 * C), &dd))) return fail(rc);
+    if ((rc = upload_slot(c, slot, (int)(2 * C), &dd))) return run.fail(rc);
     const int vf = t->dtype == MFGP_F32 ? 1 : 0;
     for (int64_t it = 0; it < C; ++it) {
       const bool ok = hipSuccess == launch_choi_select(dd + 2 * it, threshold, pts, max_points, c->stream) &&
@@ -222,27 +314,16 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
                                 : (hipSuccess == launch_inc_factor(dd + 2 * it, 1, hd[2 * it].nprod, vf, c->stream) &&
                                    hipSuccess == launch_vstream(dd + 2 * it + 1, 1, ntiles_wg(M, hd[2 * it + 1].rsplit, vf),
                                                                 vf, c->stream)));
-      if (!ok) return fail(set_err(MFGP_ERR_DEVICE, "sample_points: launch failed"));
+      if (!ok) return run.fail(set_err(MFGP_ERR_DEVICE, "sample_points: launch failed"));
     }
-    if ((rc = release_slot(c, slot))) return fail(rc);
-    int64_t st[2] = {0, 0};
-    if (hipMemcpyAsync(st, state, sizeof(st), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "sample_points: state read failed"));
-    active = (int)st[0] != 0;
-    const int64_t ran = st[1] - done;
-    done = st[1];
-    if (ran < C) {
-      // the loop stopped inside this chunk: drop the rows it did not append
-      if ((rc = mfgp_truncate(t, NH0 + done))) return fail(rc);
-    }
-    if ((rc = read_status(t))) return fail(rc);
+    if ((rc = release_slot(c, slot))) return run.fail(rc);
+    if ((rc = run.chunk_end(C))) return run.fail(rc);
+    active = (int)run.st[0] != 0;
   }
-  if (done > 0 && hipMemcpy(points, pts, sizeof(double) * 2 * done, hipMemcpyDefault) != hipSuccess)
-    return fail(set_err(MFGP_ERR_DEVICE, "sample_points: copy out failed"));
-  *count = done;
-  if ((rc = plan_leave(t, sv))) return rc;
-  return mfgp_ctx_synchronize(c);   // (the posterior's restore copy: ws is reused by the next call)
+  if (run.done > 0 && hipMemcpy(points, pts, sizeof(double) * 2 * run.done, hipMemcpyDefault) != hipSuccess)
+    return run.fail(set_err(MFGP_ERR_DEVICE, "sample_points: copy out failed"));
+  *count = run.done;
+  return run.finish(true);   // (the posterior's restore copy: ws is reused by the next call)
 }
 
 // compute_sample_points for a batch of models (the Choi planner's sample-set
@@ -251,9 +332,9 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
 // batched append + predict of every model's chosen row through the general batch
 // step -- the lattice step where the batch takes it (its kernels and the V stream's
 // honour each model's device gate, so a model past its threshold skips the rest of
-// the chunk) -- with one host synchronisation per CH iterations. Each model works on
-// its own rows past its own (sim:339's deep copy: plan_enter / plan_leave bring it
-// back); the chosen points are the single-model loop's, up to the rounding of the
+// the chunk) -- with one host synchronisation per PLAN_CHUNK iterations. Each model
+// works on its own rows past its own (sim:339's deep copy: plan_enter / plan_leave bring
+// it back); the chosen points are the single-model loop's, up to the rounding of the
 // batch step (ties decided by it).
 int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thresholds, int64_t max_points,
                              double* points, int64_t* counts) {
@@ -275,15 +356,14 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
       if (models[b2] == models[b]) return set_err(MFGP_ERR_ARG, "model %d appears twice in the batch", b);
     counts[b] = 0;
   }
-  // earlier ASYNC steps' verdicts first: the loop's decisions read the status words
-  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
-  for (int b = 0; b < count; ++b)
-    if ((rc = update_factor(models[b]))) return rc;
   mfgp_model* const* t = models;
+  if ((rc = plan_ready(c, t, count))) return rc;
   // device state: mu, var [sum M] | vmax [B] | vargmax [B] | state [B][2] | thr [B] | moff [B] |
   // Ms [B] | grids [B] | status words [B] | xn [B][2] | yn [B] | pos [B] | points [B][max_points][2] |
   // the models' saved resident posteriors
   std::vector<int64_t> moff(count), Ms(count);
+  std::vector<const double*> grids(count);
+  std::vector<const int*> stat(count);
   int64_t Mtot = 0;
   size_t nres = 0;
   for (int b = 0; b < count; ++b) {
@@ -291,75 +371,47 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
     Ms[b] = t[b]->M;
     Mtot += t[b]->M;
     nres += plan_res_doubles(t[b]);
-  }
-  const int64_t P = std::max<int64_t>(max_points, 1);
-  // one 8-byte slot per entry (pos's ints take a slot each); the offsets below are
-  // the only description of the layout, and the allocation is their end
-  const size_t B_ = (size_t)count;
-  const size_t o_mu = 0, o_var = o_mu + (size_t)Mtot, o_vmax = o_var + (size_t)Mtot, o_varg = o_vmax + B_;
-  const size_t o_state = o_varg + B_, o_thr = o_state + 2 * B_, o_moff = o_thr + B_, o_Ms = o_moff + B_;
-  const size_t o_grids = o_Ms + B_, o_stat = o_grids + B_, o_xn = o_stat + B_, o_yn = o_xn + 2 * B_, o_pos = o_yn + B_;
-  const size_t o_pts = o_pos + B_, o_res = o_pts + 2 * B_ * (size_t)P, nd = o_res + nres;
-  double* ws = nullptr;
-  if (hipMalloc(&ws, sizeof(double) * nd) != hipSuccess)
-    return set_err(MFGP_ERR_DEVICE, "batch_sample_points: out of memory");
-  std::vector<PlanSave> sv(count);
-  int entered = 0;
-  auto fail = [&](int code) {
-    for (int b = 0; b < entered; ++b) (void)plan_leave(t[b], sv[b], true);
-    (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
-    (void)hipFree(ws);
-    return code;
-  };
-  for (size_t b = 0, off = o_res; b < B_; off += plan_res_doubles(t[b]), ++b) {
-    if ((rc = plan_enter(t[b], sv[b], ws + off))) return fail(rc);
-    ++entered;
-  }
-  double* mu = ws + o_mu;
-  double* var = ws + o_var;
-  double* vmax = ws + o_vmax;
-  int64_t* vargmax = reinterpret_cast<int64_t*>(ws + o_varg);
-  int64_t* state = reinterpret_cast<int64_t*>(ws + o_state);
-  double* thr = ws + o_thr;
-  int64_t* moff_d = reinterpret_cast<int64_t*>(ws + o_moff);
-  int64_t* Ms_d = reinterpret_cast<int64_t*>(ws + o_Ms);
-  const double** grids_d = reinterpret_cast<const double**>(ws + o_grids);
-  const int** stat_d = reinterpret_cast<const int**>(ws + o_stat);
-  double* xn = ws + o_xn;
-  double* yn = ws + o_yn;
-  int* pos_d = reinterpret_cast<int*>(ws + o_pos);
-  double* pts = ws + o_pts;
-  std::vector<int64_t> st(2 * count);
-  std::vector<const double*> grids(count);
-  std::vector<const int*> stat(count);
-  for (int b = 0; b < count; ++b) {
-    st[2 * b] = 1;
-    st[2 * b + 1] = 0;
     grids[b] = t[b]->grid;
     stat[b] = t[b]->status;
   }
+  const size_t P = (size_t)std::max<int64_t>(max_points, 1);
+  const size_t dM = sizeof(double) * (size_t)Mtot, d8 = 8 * (size_t)count;   // (d8: one 8-byte entry per model)
+  WsLayout lay;
+  const size_t o_mu = lay.take(dM), o_var = lay.take(dM), o_vmax = lay.take(d8), o_varg = lay.take(d8);
+  const size_t o_state = lay.take(2 * d8), o_thr = lay.take(d8), o_moff = lay.take(d8), o_Ms = lay.take(d8);
+  const size_t o_grids = lay.take(d8), o_stat = lay.take(d8), o_xn = lay.take(2 * d8), o_yn = lay.take(d8);
+  const size_t o_pos = lay.take(sizeof(int) * count), o_pts = lay.take(2 * d8 * P);
+  const size_t o_res = lay.take(sizeof(double) * nres);
+  PlanRun run("batch_sample_points", c, t, count);
+  if (!run.own(lay.end)) return set_err(MFGP_ERR_DEVICE, "batch_sample_points: out of memory");
+  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
+  double *mu = run.at(o_mu), *var = run.at(o_var), *vmax = run.at(o_vmax), *thr = run.at(o_thr);
+  double *xn = run.at(o_xn), *yn = run.at(o_yn), *pts = run.at(o_pts);
+  int64_t *vargmax = run.at<int64_t>(o_varg), *state = run.state = run.at<int64_t>(o_state);
+  int64_t *moff_d = run.at<int64_t>(o_moff), *Ms_d = run.at<int64_t>(o_Ms);
+  const double** grids_d = run.at<const double*>(o_grids);
+  const int** stat_d = run.at<const int*>(o_stat);
+  int* pos_d = run.at<int>(o_pos);
   hipStream_t s = c->stream;
-  if (hipMemcpyAsync(state, st.data(), sizeof(int64_t) * 2 * count, hipMemcpyHostToDevice, s) != hipSuccess ||
+  if (run.open() != hipSuccess ||
       hipMemcpyAsync(thr, thresholds, sizeof(double) * count, hipMemcpyDefault, s) != hipSuccess ||
       hipMemcpyAsync(moff_d, moff.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(Ms_d, Ms.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(grids_d, grids.data(), sizeof(double*) * count, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(stat_d, stat.data(), sizeof(int*) * count, hipMemcpyHostToDevice, s) != hipSuccess)
-    return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: state upload failed"));
+    return run.fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: state upload failed"));
   // the initial posteriors and their max / argmax (sim:340-342)
   if ((rc = batch_run(const_cast<mfgp_model**>(t), count, nullptr, nullptr, nullptr, mu, var, vmax, vargmax, 0,
                       false, true)))
-    return fail(rc);
+    return run.fail(rc);
   for (int b = 0; b < count; ++b) t[b]->gate_dev = reinterpret_cast<int*>(state + 2 * b);
-  // the models still running (the batch step's members; a stopped one leaves at the
-  // next chunk boundary), their offsets into mu / var and indices into vmax
-  std::vector<int> live(count);
-  for (int b = 0; b < count; ++b) live[b] = b;
-  constexpr int64_t CH = 32;
+  // run.live: the models still running (the batch step's members; a stopped one leaves
+  // at the next chunk boundary), their offsets into mu / var and indices into vmax
+  std::vector<int>& live = run.live;
   int64_t it_done = 0;
   const auto tp1 = std::chrono::steady_clock::now();
   while (!live.empty() && it_done < max_points) {
-    const int64_t C = std::min<int64_t>(CH, max_points - it_done);
+    const int64_t C = std::min<int64_t>(PLAN_CHUNK, max_points - it_done);
     // the live models are the batch step's members, in batch order: their rows at
     // their member places (pos), their outputs at their own offsets / indices
     std::vector<mfgp_model*> lm;
@@ -373,40 +425,33 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
       lvi.push_back(b);
     }
     if (hipMemcpyAsync(pos_d, pos.data(), sizeof(int) * count, hipMemcpyHostToDevice, s) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: upload failed"));
+      return run.fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: upload failed"));
     for (int64_t it = 0; it < C; ++it) {
       if (launch_choi_select_batch(count, pos_d, state, stat_d, thr, vmax, vargmax, mu, moff_d, grids_d, Ms_d, xn, yn,
                                    pts, max_points, s) != hipSuccess)
-        return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: launch failed"));
+        return run.fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: launch failed"));
       if ((int)lm.size() == count)
         rc = batch_run(lm.data(), count, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true);
       else
         rc = batch_run(lm.data(), (int)lm.size(), xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true,
                        loff.data(), lvi.data());
-      if (rc) return fail(rc);
+      if (rc) return run.fail(rc);
     }
     it_done += C;
-    if (hipMemcpyAsync(st.data(), state, sizeof(int64_t) * 2 * count, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: state read failed"));
-    for (int b : live)
-      if ((rc = read_status(t[b]))) return fail(rc);
+    if ((rc = run.chunk_end())) return run.fail(rc);
     std::vector<int> keep;
     for (int b : live)
-      if ((int)st[2 * b] != 0) keep.push_back(b);
+      if ((int)run.st[2 * b] != 0) keep.push_back(b);
     live.swap(keep);
   }
   const auto tp2 = std::chrono::steady_clock::now();
   for (int b = 0; b < count; ++b) {
-    counts[b] = st[2 * b + 1];
-    if (counts[b] > 0 && hipMemcpy(points + 2 * (size_t)b * (size_t)P, pts + 2 * (size_t)b * (size_t)P,
-                                   sizeof(double) * 2 * counts[b], hipMemcpyDefault) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: copy out failed"));
+    counts[b] = run.st[2 * b + 1];
+    if (counts[b] > 0 && hipMemcpy(points + 2 * (size_t)b * P, pts + 2 * (size_t)b * P, sizeof(double) * 2 * counts[b],
+                                   hipMemcpyDefault) != hipSuccess)
+      return run.fail(set_err(MFGP_ERR_DEVICE, "batch_sample_points: copy out failed"));
   }
-  for (int b = 0; b < count; ++b) (void)plan_leave(t[b], sv[b]);
-  entered = 0;
-  const bool sync_ok = hipStreamSynchronize(s) == hipSuccess;   // (the restore copies read ws)
-  (void)hipFree(ws);
+  const bool left = run.finish(false) == MFGP_OK;
   const auto tp3 = std::chrono::steady_clock::now();
   auto us = [](std::chrono::steady_clock::duration dt) {
     return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(dt).count();
@@ -414,7 +459,7 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   c->plan_stats[8] += us(tp1 - tp0);
   c->plan_stats[9] += us(tp2 - tp1);
   c->plan_stats[10] += us(tp3 - tp2);
-  return sync_ok ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "batch_sample_points: restore failed");
+  return left ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "batch_sample_points: restore failed");
 }
 
 // The greedy integrated-variance planner (mfgp_plan_ivr.hip): n_points cells chosen one
@@ -432,6 +477,7 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
 int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t* cand, int64_t nc,
                   int64_t n_points, double min_gain, int refresh, int64_t* cells, double* points, double* gains,
                   int64_t* count) {
+  const char* who = "mfgp_plan_ivr";
   const Entry entry(model);
   int rc = entry.rc;
   if (rc) return rc;
@@ -442,33 +488,23 @@ int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t
   if (n_points < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative n_points");
   if (refresh < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative refresh");
   if (n_points > 0 && (!cells || !points || !gains)) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: null output");
-  if (t->dtype != MFGP_F64)
-    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
-  if (M <= 0 || !t->grid) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the model has no grid (mfgp_set_grid)");
+  if ((rc = need_f64_grid(t, who))) return rc;
   if (!c->incremental) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr needs incremental updates enabled");
   if (w && ldw < M)
     return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: ldw = %lld is less than M = %lld", (long long)ldw, (long long)M);
   if (nc < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative candidate count");
-  if (!cand && nc != M)
-    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: a NULL candidate list means all %lld cells (got nc = %lld)",
-                   (long long)M, (long long)nc);
-  for (int64_t j = 0; cand && j < nc; ++j)
-    if (cand[j] < 0 || cand[j] >= M)
-      return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: cand[%lld] = %lld is outside the grid's cells [0, %lld)",
-                     (long long)j, (long long)cand[j], (long long)M);
+  if ((rc = check_cells(who, "cand", cand, nc, M))) return rc;
   const bool w_host = w && !is_device_ptr(w);
-  if (w_host && !all_finite(w, M)) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the weights must be finite");
+  if (w_host && finite_rows(w, 1, ldw, M) >= 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the weights must be finite");
   if (ivr_segments(M) > 65535)
     return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: grids of at most %lld cells are supported",
                    (long long)65535 * IVR_SEG * PBM);
   *count = 0;
   if (n_points == 0 || nc == 0) return MFGP_OK;
-  // earlier ASYNC steps' verdicts first: the loop's decisions read the status word
-  if (!c->async_status.empty() && (rc = mfgp_ctx_synchronize(c))) return rc;
-  if ((rc = update_factor(t))) return rc;
-  if ((rc = ensure_resident_v(t, "mfgp_plan_ivr"))) return rc;
-  const int64_t NH0 = t->NH, N0 = t->NL + t->NH;
-  if ((rc = ensure_cap(t, N0 + std::min<int64_t>(n_points, 32))) || (rc = ensure_v(t))) return rc;
+  if ((rc = plan_ready(c, &t, 1))) return rc;
+  if ((rc = ensure_resident_v(t, who))) return rc;
+  const int64_t N0 = t->NL + t->NH;
+  if ((rc = ensure_cap(t, N0 + std::min<int64_t>(n_points, PLAN_CHUNK))) || (rc = ensure_v(t))) return rc;
   // device state (the context's workspace serves the lattice step): mu, var, S, g, x [M] | tau's
   // partials | vmax | vargmax | state {gate, count} | xn [2] | yn | cells, gains [P] | points [P][2] |
   // cand | host weights | k_ivr_partial's partials | the covariance product's scratch | the
@@ -486,54 +522,37 @@ int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t
   const size_t o_part = lay.take(sizeof(double) * (size_t)nseg * M);
   const size_t o_work = lay.take(cov_work_bytes(t, N0 + P));
   const size_t o_res = lay.take(sizeof(double) * plan_res_doubles(t));
-  char* ws = nullptr;
-  if (hipMalloc(&ws, lay.end) != hipSuccess) {
-    (void)hipGetLastError();
+  PlanRun run(who, c, &t, 1);
+  if (!run.own(lay.end))
     return set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: out of memory (%zu bytes of scratch)", lay.end);
-  }
-  auto at = [&](size_t o) { return reinterpret_cast<double*>(ws + o); };
-  double *mu_s = at(o_mu), *var_s = at(o_var), *S = at(o_S), *g = at(o_g), *x = at(o_x), *tau = at(o_tau);
-  double* vmax = at(o_misc);
+  double *mu_s = run.at(o_mu), *var_s = run.at(o_var), *S = run.at(o_S), *g = run.at(o_g), *x = run.at(o_x);
+  double *tau = run.at(o_tau), *vmax = run.at(o_misc);
   int64_t* vargmax = reinterpret_cast<int64_t*>(vmax + 1);
-  int64_t* state = vargmax + 1;
+  int64_t* state = run.state = vargmax + 1;
   double *xn = reinterpret_cast<double*>(state + 2), *yn = xn + 2;
   int* gate = reinterpret_cast<int*>(state);
-  int64_t* dcells = reinterpret_cast<int64_t*>(ws + o_cells);
-  int64_t* dcand = cand ? reinterpret_cast<int64_t*>(ws + o_cand) : nullptr;
+  int64_t* dcand = cand ? run.at<int64_t>(o_cand) : nullptr;
   hipStream_t s = c->stream;
-  PlanSave sv;
-  bool entered = false;
-  auto fail = [&](int code) {
-    if (entered) (void)plan_leave(t, sv, true);
-    (void)hipStreamSynchronize(s);   // (the restore copies read ws)
-    (void)hipFree(ws);
-    return code;
-  };
-  if ((rc = plan_enter(t, sv, at(o_res)))) return fail(rc);
-  entered = true;
-  const double* dw = w;
-  if (w_host) {
-    if (hipMemcpyAsync(at(o_w), w, sizeof(double) * M, hipMemcpyHostToDevice, s) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
-    dw = at(o_w);
-  }
-  const int64_t st0[2] = {1, 0};
-  if ((cand && hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      hipMemcpyAsync(state, st0, sizeof(st0), hipMemcpyHostToDevice, s) != hipSuccess)
-    return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
+  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
+  const StagedIn sw(w, 1, M, ldw, w_host, run.at(o_w));
+  const double* dw = sw.dev;
+  if (sw.upload(s) != hipSuccess ||
+      (cand && hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      run.open() != hipSuccess)
+    return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
   // the initial posterior, and S_0
   if ((rc = batch_run(&t, 1, nullptr, nullptr, nullptr, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, false, true)))
-    return fail(rc);
+    return run.fail(rc);
   auto numerators = [&]() -> int {
     GPDesc d;
     fill_desc(d, t);
-    HIP_TRY(launch_ivr_partial(d, nullptr, M, dw, 1, M, at(o_part), s));
-    HIP_TRY(launch_plan_ssum(at(o_part), (int)nseg, M, S, s));
+    HIP_TRY(launch_ivr_partial(d, nullptr, M, dw, 1, M, run.at(o_part), s));
+    HIP_TRY(launch_plan_ssum(run.at(o_part), (int)nseg, M, S, s));
     return MFGP_OK;
   };
-  if ((rc = numerators())) return fail(rc);
+  if ((rc = numerators())) return run.fail(rc);
   CovWork cw;
-  if ((rc = cov_work_init(t, ws + o_work, N0 + P, cw))) return fail(rc);
+  if ((rc = cov_work_init(t, run.ws + o_work, N0 + P, cw))) return run.fail(rc);
   cw.a.x = x;
   cw.a.S = S;
   cw.a.g = g;
@@ -555,53 +574,38 @@ int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t
   q.status = t->status;
   q.xn = xn;
   q.yn = yn;
-  q.cells = dcells;
-  q.gains = at(o_gains);
-  q.pts = at(o_pts);
+  q.cells = run.at<int64_t>(o_cells);
+  q.gains = run.at(o_gains);
+  q.pts = run.at(o_pts);
   t->gate_dev = gate;
-  int64_t done = 0;
+  const int64_t& done = run.done;
   bool active = true;
-  constexpr int64_t CH = 32;   // iterations per chunk
   const int64_t one = 1;
   while (active && done < n_points) {
-    int64_t C = std::min<int64_t>(CH, n_points - done);
+    int64_t C = std::min<int64_t>(PLAN_CHUNK, n_points - done);
     if (refresh > 0) C = std::min<int64_t>(C, refresh - done % refresh);
-    const int64_t N = t->NL + t->NH;
-    if ((rc = ensure_cap(t, N + C)) || (rc = ensure_v(t))) return fail(rc);
-    if (!factor_current(t)) return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: factor lost on growth"));
+    if ((rc = run.grow(t, C))) return run.fail(rc);
     q.status = t->status;
-    if (refresh > 0 && done > 0 && done % refresh == 0 && (rc = numerators())) return fail(rc);
+    if (refresh > 0 && done > 0 && done % refresh == 0 && (rc = numerators())) return run.fail(rc);
     for (int64_t it = 0; it < C; ++it) {
-      if (launch_ivr_pick(q, s) != hipSuccess) return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
-      if ((rc = batch_run(&t, 1, xn, yn, &one, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, true, true))) return fail(rc);
+      if (launch_ivr_pick(q, s) != hipSuccess) return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
+      if ((rc = batch_run(&t, 1, xn, yn, &one, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, true, true))) return run.fail(rc);
       if (done + it + 1 >= n_points) break;   // the last pick: no score is read after it
       const int64_t row = t->NL + t->NH - 1;
       if (launch_plan_x(static_cast<const double*>(t->V), t->vld, row, M, dw, g, x, tau, gate, s) != hipSuccess)
-        return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
-      if ((rc = cov_work_run(t, cw, row + 1))) return fail(rc);
+        return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
+      if ((rc = cov_work_run(t, cw, row + 1))) return run.fail(rc);
     }
-    int64_t st[2] = {0, 0};
-    if (hipMemcpyAsync(st, state, sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: state read failed"));
-    active = (int)st[0] != 0;
-    const int64_t ran = st[1] - done;
-    done = st[1];
-    if (ran < C) {
-      // the loop stopped inside this chunk: drop the rows it did not append
-      if ((rc = mfgp_truncate(t, NH0 + done))) return fail(rc);
-    }
-    if ((rc = read_status(t))) return fail(rc);
+    if ((rc = run.chunk_end(C))) return run.fail(rc);
+    active = (int)run.st[0] != 0;
   }
-  if (done > 0 && (hipMemcpy(cells, dcells, sizeof(int64_t) * done, hipMemcpyDeviceToHost) != hipSuccess ||
+  if (done > 0 && (hipMemcpy(cells, q.cells, sizeof(int64_t) * done, hipMemcpyDeviceToHost) != hipSuccess ||
                    hipMemcpy(gains, q.gains, sizeof(double) * done, hipMemcpyDeviceToHost) != hipSuccess ||
                    hipMemcpy(points, q.pts, sizeof(double) * 2 * done, hipMemcpyDefault) != hipSuccess))
-    return fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: copy out failed"));
+    return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: copy out failed"));
   *count = done;
-  (void)plan_leave(t, sv);
-  const bool sync_ok = mfgp_ctx_synchronize(c) == MFGP_OK;   // (the posterior's restore copy reads ws)
-  (void)hipFree(ws);
-  return sync_ok ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: restore failed");
+  // (the posterior's restore copy reads ws)
+  return run.finish(true) == MFGP_OK ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: restore failed");
 }
 
 // Voronoi-cell reductions (simulator.py:194-323) on the device. Inputs may be

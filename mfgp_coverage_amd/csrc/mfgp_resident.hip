@@ -2,7 +2,8 @@
 // integrated variance reduction (mfgp_ivr.hip), look-ahead and off-grid queries
 // (mfgp_look.hip) and pathwise samples (mfgp_sample.hip). Each brings V over all N
 // rows first (ensure_resident_v), lays its scratch out in the context's workspace
-// (WsLayout) and stages outputs bound for host memory there (StagedOut).
+// (WsLayout) and stages matrices the caller holds in host memory there (StagedIn,
+// StagedOut). The argument checks they share are need_f64_grid, check_cells, finite_rows.
 #include <cmath>
 #include <cstring>
 
@@ -11,7 +12,7 @@
 using namespace mfgp;
 using namespace mfgp_host;
 
-namespace mfgp_host {
+namespace mfgp_host __attribute__((visibility("hidden"))) {   // (as in mfgp_host.h: the definitions too)
 
 // V holds all N rows of the current factor, hyperparameters and grid: the state
 // every predict path leaves (mfgp_cov_block reads rows [0, N) of it).
@@ -38,6 +39,30 @@ bool all_finite(const double* p, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
     if (!std::isfinite(p[i])) return false;
   return true;
+}
+
+int need_f64_grid(const mfgp_model* m, const char* who) {
+  if (m->dtype != MFGP_F64)
+    return set_err(MFGP_ERR_ARG, "%s: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model", who);
+  if (m->M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "%s: the model has no grid (mfgp_set_grid)", who);
+  return MFGP_OK;
+}
+
+int check_cells(const char* who, const char* name, const int64_t* list, int64_t n, int64_t M) {
+  if (!list && n != M)
+    return set_err(MFGP_ERR_ARG, "%s: a NULL candidate list means all %lld cells (got nc = %lld)", who, (long long)M,
+                   (long long)n);
+  for (int64_t i = 0; list && i < n; ++i)
+    if (list[i] < 0 || list[i] >= M)
+      return set_err(MFGP_ERR_ARG, "%s: %s[%lld] = %lld is outside the grid's cells [0, %lld)", who, name, (long long)i,
+                     (long long)list[i], (long long)M);
+  return MFGP_OK;
+}
+
+int64_t finite_rows(const double* p, int64_t rows, int64_t ld, int64_t cols) {
+  for (int64_t r = 0; r < rows; ++r)
+    if (!all_finite(p + r * ld, cols)) return r;
+  return -1;
 }
 
 // K** x by the axis products: a lattice grid with both axes within KSS_AXIS_MAX
@@ -117,9 +142,7 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
   int rc = entry.rc;
   if (rc) return rc;
   mfgp_ctx* c = m->ctx;
-  if (m->dtype != MFGP_F64)
-    return set_err(MFGP_ERR_ARG, "mfgp_cov_block: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
-  if (m->M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: the model has no grid (mfgp_set_grid)");
+  if ((rc = need_f64_grid(m, "mfgp_cov_block"))) return rc;
   if (na < 0 || nb < 0) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: negative block size");
   if ((!rows && na != m->M) || (!cols && nb != m->M))
     return set_err(MFGP_ERR_ARG, "mfgp_cov_block: a NULL index list means all %lld cells (got na = %lld, nb = %lld)",
@@ -129,14 +152,9 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
   if (ldo < nb)
     return set_err(MFGP_ERR_ARG, "mfgp_cov_block: ldo = %lld is less than nb = %lld", (long long)ldo, (long long)nb);
   if ((na + 63) / 64 > 65535) return set_err(MFGP_ERR_ARG, "mfgp_cov_block: at most %d rows per call", 65535 * 64);
-  for (int s = 0; s < 2; ++s) {
-    const int64_t* l = s ? cols : rows;
-    const int64_t n = s ? nb : na;
-    for (int64_t i = 0; l && i < n; ++i)
-      if (l[i] < 0 || l[i] >= m->M)
-        return set_err(MFGP_ERR_ARG, "mfgp_cov_block: %s[%lld] = %lld is outside the grid's cells [0, %lld)",
-                       s ? "cols" : "rows", (long long)i, (long long)l[i], (long long)m->M);
-  }
+  if ((rc = check_cells("mfgp_cov_block", "rows", rows, na, m->M)) ||
+      (rc = check_cells("mfgp_cov_block", "cols", cols, nb, m->M)))
+    return rc;
   const bool prior = (flags & MFGP_COV_PRIOR) != 0;
   if (!prior && (rc = ensure_resident_v(m, "mfgp_cov_block"))) return rc;
   // workspace: [rows | cols | the block, when out is host memory]
@@ -173,14 +191,9 @@ int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const dou
   if (rc) return rc;
   mfgp_ctx* c = m->ctx;
   const int64_t M = m->M;
-  if (m->dtype != MFGP_F64)
-    return set_err(MFGP_ERR_ARG,
-                   "mfgp_var_reduction: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
-  if (M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: the model has no grid (mfgp_set_grid)");
+  if ((rc = need_f64_grid(m, "mfgp_var_reduction"))) return rc;
   if (nc < 0) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: negative candidate count");
-  if (!cand && nc != M)
-    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: a NULL candidate list means all %lld cells (got nc = %lld)",
-                   (long long)M, (long long)nc);
+  if (!cand && (rc = check_cells("mfgp_var_reduction", "cand", nullptr, nc, M))) return rc;   // (the entries: below)
   if (nw < 1 || nw > MFGP_IVR_MAXW)
     return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: nw = %d is outside [1, %d]", nw, MFGP_IVR_MAXW);
   if (!w && nw != 1)
@@ -192,14 +205,10 @@ int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const dou
   if (ivr_segments(M) > 65535)
     return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: grids of at most %lld cells are supported",
                    (long long)65535 * IVR_SEG * PBM);
-  for (int64_t j = 0; cand && j < nc; ++j)
-    if (cand[j] < 0 || cand[j] >= M)
-      return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: cand[%lld] = %lld is outside the grid's cells [0, %lld)",
-                     (long long)j, (long long)cand[j], (long long)M);
+  if ((rc = check_cells("mfgp_var_reduction", "cand", cand, nc, M))) return rc;
   const bool w_host = w && !is_device_ptr(w);
-  for (int k = 0; w_host && k < nw; ++k)
-    if (!all_finite(w + (int64_t)k * ldw, M))
-      return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: the weights must be finite (vector %d)", k);
+  if (const int64_t k = w_host ? finite_rows(w, nw, ldw, M) : -1; k >= 0)
+    return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: the weights must be finite (vector %d)", (int)k);
   if (nc == 0) return MFGP_OK;
   if (!out) return set_err(MFGP_ERR_ARG, "mfgp_var_reduction: null output");
   if ((rc = ensure_resident_v(m, "mfgp_var_reduction"))) return rc;
@@ -221,21 +230,14 @@ int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const dou
   char* ws = reinterpret_cast<char*>(c->ws);
   int64_t* dcand = cand ? reinterpret_cast<int64_t*>(ws + o_cand) : nullptr;
   if (cand) HIP_TRY(hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, c->stream));
-  const double* dw = w;
-  int64_t dldw = ldw;
-  if (w_host) {
-    double* p = reinterpret_cast<double*>(ws + o_w);
-    HIP_TRY(hipMemcpy2DAsync(p, sizeof(double) * M, w, sizeof(double) * ldw, sizeof(double) * M, nw,
-                             hipMemcpyHostToDevice, c->stream));
-    dw = p;
-    dldw = M;
-  }
+  const StagedIn sw(w, nw, M, ldw, w_host, ws + o_w);
+  HIP_TRY(sw.upload(c->stream));
   const StagedOut so(out, ldo, o_host, ws + o_out, nc);
   double* dbest = want_best ? reinterpret_cast<double*>(ws + o_best) : nullptr;
   int64_t* dbp = want_best ? reinterpret_cast<int64_t*>(ws + o_bp) : nullptr;
   GPDesc d;
   fill_desc(d, m);
-  HIP_TRY(launch_ivr(d, dcand, nc, dw, nw, dldw, reinterpret_cast<double*>(ws + o_part), so.dev, so.ld,
+  HIP_TRY(launch_ivr(d, dcand, nc, sw.dev, nw, sw.ld, reinterpret_cast<double*>(ws + o_part), so.dev, so.ld,
                      reinterpret_cast<double*>(ws + o_bval), reinterpret_cast<int64_t*>(ws + o_bpos), dbest, dbp,
                      c->stream));
   HIP_TRY(so.copy_back(nc, nw, c->stream));
@@ -254,9 +256,7 @@ int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* 
   if (rc) return rc;
   mfgp_ctx* c = m->ctx;
   const int64_t M = m->M;
-  if (m->dtype != MFGP_F64)
-    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model");
-  if (M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: the model has no grid (mfgp_set_grid)");
+  if ((rc = need_f64_grid(m, "mfgp_cov_apply"))) return rc;
   if (nx < 1 || nx > MFGP_IVR_MAXW)
     return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: nx = %d is outside [1, %d]", nx, MFGP_IVR_MAXW);
   if (!x || !out) return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: null vectors / output");
@@ -265,9 +265,8 @@ int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* 
   if (ldo < M)
     return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: ldo = %lld is less than M = %lld", (long long)ldo, (long long)M);
   const bool x_host = !is_device_ptr(x);
-  for (int k = 0; x_host && k < nx; ++k)
-    if (!all_finite(x + (int64_t)k * ldx, M))
-      return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: the vectors must be finite (column %d)", k);
+  if (const int64_t k = x_host ? finite_rows(x, nx, ldx, M) : -1; k >= 0)
+    return set_err(MFGP_ERR_ARG, "mfgp_cov_apply: the vectors must be finite (column %d)", (int)k);
   const bool prior = (flags & MFGP_COV_PRIOR) != 0;
   if (!prior && (rc = ensure_resident_v(m, "mfgp_cov_apply"))) return rc;
   const int64_t N = prior ? 0 : m->NL + m->NH;
@@ -279,20 +278,13 @@ int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* 
   const size_t o_work = lay.take(cov_work_bytes(m, N));
   if ((rc = ensure_ws(c, lay.end))) return rc;
   char* ws = reinterpret_cast<char*>(c->ws);
-  const double* dx = x;
-  int64_t dldx = ldx;
-  if (x_host) {
-    double* p = reinterpret_cast<double*>(ws + o_x);
-    HIP_TRY(hipMemcpy2DAsync(p, sizeof(double) * M, x, sizeof(double) * ldx, sizeof(double) * M, nx,
-                             hipMemcpyHostToDevice, c->stream));
-    dx = p;
-    dldx = M;
-  }
+  const StagedIn sx(x, nx, M, ldx, x_host, ws + o_x);
+  HIP_TRY(sx.upload(c->stream));
   const StagedOut so(out, ldo, o_host, ws + o_out, M);
   CovWork w;
   if ((rc = cov_work_init(m, ws + o_work, N, w))) return rc;
   for (int k = 0; k < nx; ++k) {
-    w.a.x = dx + (int64_t)k * dldx;
+    w.a.x = sx.dev + (int64_t)k * sx.ld;
     w.a.u = so.dev + (int64_t)k * so.ld;
     if ((rc = cov_work_run(m, w, N))) return rc;
   }
@@ -523,9 +515,7 @@ int mfgp_sample_axis_factor(const double* axis, int n, double lengthscale, doubl
 // model serves samples (fp64, a lattice grid within the sampler's sizes) and its sample
 // record holds the axis factors of the current serial.
 static int sample_record(mfgp_model* m, const char* who) {
-  if (m->dtype != MFGP_F64)
-    return set_err(MFGP_ERR_ARG, "%s: MFGP_F32 models (fp32 V) are not supported; use an MFGP_F64 model", who);
-  if (m->M <= 0 || !m->grid) return set_err(MFGP_ERR_ARG, "%s: the model has no grid (mfgp_set_grid)", who);
+  if (const int rc = need_f64_grid(m, who)) return rc;
   const GridLattice& L = m->lat;
   if (L.nx <= 0 || L.ny <= 0)
     return set_err(MFGP_ERR_NO_LATTICE, "%s: the grid is not a lattice of two axes", who);
@@ -666,9 +656,9 @@ int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64
   if (S > 0 && (!out || (nz > 0 && !normals))) return set_err(MFGP_ERR_ARG, "%s: null normals / output", who);
   const bool z_dev = S > 0 && nz > 0 && is_device_ptr(normals);
   const bool o_dev = S > 0 && is_device_ptr(out);
-  if (!z_dev && nz > 0)
-    for (int64_t s = 0; s < S; ++s)
-      if (!all_finite(normals + s * ldz, nz)) return set_err(MFGP_ERR_ARG, "%s: the normals must be finite", who);
+  const bool z_host = !z_dev && nz > 0;   // the normals are staged chunk by chunk
+  if (z_host && finite_rows(normals, S, ldz, nz) >= 0)
+    return set_err(MFGP_ERR_ARG, "%s: the normals must be finite", who);
   const int64_t tw = std::max(std::max(k->ry[0], k->ry[1]), 1);
   const size_t t_bytes = sizeof(double) * (size_t)SAMPLE_CHUNK * k->fields * k->nx * tw;
   if (t_bytes > SAMPLE_T_MAX)
@@ -734,16 +724,10 @@ int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64
   for (int64_t s0 = 0; s0 < S; s0 += SAMPLE_CHUNK) {
     const int64_t sc = std::min<int64_t>(SAMPLE_CHUNK, S - s0);
     a.Sc = (int)sc;
-    if (z_dev || nz == 0) {
-      a.Z = normals ? normals + s0 * ldz : nullptr;
-      a.ldz = ldz;
-    } else {
-      double* dz = reinterpret_cast<double*>(ws + o_z);
-      HIP_TRY(hipMemcpy2DAsync(dz, sizeof(double) * nz, normals + s0 * ldz, sizeof(double) * ldz, sizeof(double) * nz,
-                               sc, hipMemcpyHostToDevice, c->stream));
-      a.Z = dz;
-      a.ldz = nz;
-    }
+    const StagedIn sz(normals ? normals + s0 * ldz : nullptr, sc, nz, ldz, z_host, ws + o_z);
+    HIP_TRY(sz.upload(c->stream));
+    a.Z = sz.dev;
+    a.ldz = sz.ld;
     const StagedOut so(out + s0 * ldo, ldo, !o_dev, ws + o_o, M);
     a.out = so.dev;
     a.ldo = so.ld;
@@ -756,7 +740,7 @@ int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64
       m->cnt[N_SAMPLE_GEMM] += 1;
     }
     HIP_TRY(so.copy_back(M, sc, c->stream));
-    if (!o_dev || !(z_dev || nz == 0)) HIP_TRY(hipStreamSynchronize(c->stream));   // the staging is reused by the next chunk
+    if (!o_dev || z_host) HIP_TRY(hipStreamSynchronize(c->stream));   // the staging is reused by the next chunk
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   return MFGP_OK;
