@@ -22,6 +22,9 @@ It restates, in NumPy, the single hot path of MSU-dcypherlab/mfgp-coverage
   ``nlml_extended``       the same formula wholly in 80-bit long double, the yardstick
                           of both ``nlml`` and mfgp_nlml at tile edges
                           (tests/golden/make_nlml_edges_golden.py).
+* ``posterior_extended``  ``sf_diag`` / ``mf_diag`` wholly in 80-bit long double, the
+                          yardstick of both and of every device route to the posterior
+                          at tile edges (tests/golden/make_posterior_edges_golden.py).
 
 Pinning: ``tests/test_oracle.py`` checks this module
 against golden vectors produced by importing the reference itself in the build
@@ -453,10 +456,85 @@ def _log_ld(x):
     return y
 
 
-def _sq_dist_scaled_ld(x, log_l):
+def _sq_dist_scaled_ld(x, log_l, xp=None):
+    """Squared distances of the rows of x to those of xp (default: x), scaled as se_kernel does."""
     lx = _exp_ld(log_l)
-    d = x[:, None, :] / lx - x[None, :, :] / lx
+    d = x[:, None, :] / lx - (x if xp is None else xp)[None, :, :] / lx
     return np.sum(d * d, axis=2)
+
+
+def _mf_parts_ld(NL, N, rho, snL, snH):
+    """The MF block structure over NL lofi rows and N - NL hifi rows, shared by nlml_extended and
+    posterior_extended: the masks (lo, hi, ll, hh), the coefficients cL (1 | rho | rho^2) and
+    cH (0 | 1) of the lofi and hifi kernels in K, and the noise diagonal."""
+    lo = np.zeros(N, dtype=bool)
+    lo[:NL] = True
+    hi = ~lo
+    ll, hh = lo[:, None] & lo[None, :], hi[:, None] & hi[None, :]
+    cL = np.where(ll, LD(1), np.where(hh, rho * rho, rho)).astype(LD)
+    cH = np.where(hh, LD(1), LD(0)).astype(LD)
+    return lo, hi, ll, hh, cL, cH, np.diag(np.where(lo, snL, snH))
+
+
+def _posterior_parts_ld(XL, yL, XH, yH, hyp, Xs, jitter=JITTER):
+    """(K [N, N], psi [M, N], r [N], mean, k**) of the posterior in longdouble: the SF / MF
+    assembly of posterior_extended (K with the noise and the jitter on its diagonal)."""
+    _require_extended()
+    hyp = np.asarray(hyp, dtype=np.float64).astype(LD)
+    XL = np.asarray(XL, dtype=np.float64).reshape(-1, 2).astype(LD)
+    XH = np.asarray(XH, dtype=np.float64).reshape(-1, 2).astype(LD)
+    yL = np.asarray(yL, dtype=np.float64).reshape(-1).astype(LD)
+    yH = np.asarray(yH, dtype=np.float64).reshape(-1).astype(LD)
+    Xs = np.asarray(Xs, dtype=np.float64).reshape(-1, 2).astype(LD)
+    jit, half = LD(jitter), LD(0.5)
+    if hyp.shape[0] == 4:
+        mean, s, sn = _exp_ld(hyp[0]), _exp_ld(hyp[1]), _exp_ld(hyp[3])
+        N = XH.shape[0]
+        eye = np.eye(N, dtype=LD)
+        K = s * _exp_ld(-half * _sq_dist_scaled_ld(XH, hyp[2])) + eye * sn + eye * jit
+        psi = s * _exp_ld(-half * _sq_dist_scaled_ld(Xs, hyp[2], XH))
+        res, kss = yH - mean, s
+    else:
+        mL, sL, sH = _exp_ld(hyp[0]), _exp_ld(hyp[1]), _exp_ld(hyp[4])
+        rho, snL, snH = _exp_ld(hyp[6]), _exp_ld(hyp[7]), _exp_ld(hyp[8])
+        mean = rho * mL + _exp_ld(hyp[3])
+        NL, NH = XL.shape[0], XH.shape[0]
+        N = NL + NH
+        Xa = np.vstack([XL, XH])
+        lo, hi, _, _, cL, cH, noise = _mf_parts_ld(NL, N, rho, snL, snH)
+        K = cL * (sL * _exp_ld(-half * _sq_dist_scaled_ld(Xa, hyp[2]))) + \
+            cH * (sH * _exp_ld(-half * _sq_dist_scaled_ld(Xa, hyp[5]))) + noise + np.eye(N, dtype=LD) * jit
+        # a grid cell is a hifi point: its columns of K's last block row
+        pL = np.where(lo, rho, rho * rho).astype(LD)[None, :]
+        pH = np.where(hi, LD(1), LD(0)).astype(LD)[None, :]
+        psi = pL * (sL * _exp_ld(-half * _sq_dist_scaled_ld(Xs, hyp[2], Xa))) + \
+            pH * (sH * _exp_ld(-half * _sq_dist_scaled_ld(Xs, hyp[5], Xa)))
+        res, kss = np.concatenate([yL - mL, yH - mean]), rho * rho * sL + sH
+    return K, psi, res, mean, kss
+
+
+def posterior_extended(XL, yL, XH, yH, hyp, Xs, jitter=JITTER):
+    """sf_diag / mf_diag (hyp [4]: XL / yL empty; hyp [9]: MF) evaluated wholly in
+    np.longdouble: kernel assembly with _exp_ld, _chol_ld, V = L^-1 psi^T and z = L^-1 r by
+    _fwd_ld, mu = mean + V^T z, var = k** - colsum(V o V). The float64 inputs are taken as
+    exact; N = 0 gives the prior. Returns (mu [M], var [M], k**) as longdouble -- the
+    yardstick of the fp64 oracle and of every device route to the posterior at tile edges
+    (tests/golden/make_posterior_edges_golden.py). No libm function is called. Raises
+    RuntimeError where longdouble is no wider than 64 bits of mantissa, LinAlgError on a
+    K that is not positive definite."""
+    K, psi, res, mean, kss = _posterior_parts_ld(XL, yL, XH, yH, hyp, Xs, jitter)
+    N = K.shape[0]
+    M = psi.shape[0]
+    if N == 0:
+        return np.full(M, mean, dtype=LD), np.full(M, kss, dtype=LD), kss
+    assert K.dtype == LD and psi.dtype == LD and res.dtype == LD
+    L = _chol_ld(K)
+    V = _fwd_ld(L, np.ascontiguousarray(psi.T))
+    z = _fwd_ld(L, res)
+    mu = mean + V.T @ z
+    var = kss - np.sum(V * V, axis=0)
+    assert mu.dtype == LD and var.dtype == LD
+    return mu, var, kss
 
 
 def nlml_extended(X, y, hyp, XL=None, yL=None, jitter=JITTER):
@@ -494,14 +572,9 @@ def nlml_extended(X, y, hyp, XL=None, yL=None, jitter=JITTER):
         rH2 = _sq_dist_scaled_ld(Xa, hyp[5])
         EL = sL * _exp_ld(-half * rL2)
         EH = sH * _exp_ld(-half * rH2)
-        lo = np.zeros(N, dtype=bool)
-        lo[:NL] = True
-        hi = ~lo
-        ll, hh = lo[:, None] & lo[None, :], hi[:, None] & hi[None, :]
+        lo, hi, ll, hh, cL, cH, noise = _mf_parts_ld(NL, N, rho, snL, snH)
         zero = LD(0)
-        cL = np.where(ll, one, np.where(hh, rho * rho, rho)).astype(LD)
-        cH = np.where(hh, one, zero).astype(LD)
-        K = cL * EL + cH * EH + np.diag(np.where(lo, snL, snH)) + np.eye(N, dtype=LD) * jit
+        K = cL * EL + cH * EH + noise + np.eye(N, dtype=LD) * jit
         res = np.concatenate([yL - mL, y - mH])
         drho = np.where(ll, zero, np.where(hh, two * rho * rho, rho)).astype(LD)
         oL, oH = np.ones(NL, dtype=LD), np.ones(NH, dtype=LD)
