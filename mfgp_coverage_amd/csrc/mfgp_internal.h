@@ -196,9 +196,6 @@ hipError_t launch_predict(const GPDesc* d, int count, int64_t max_ctiles, hipStr
 hipError_t set_stamps(long long* p);
 #endif
 hipError_t launch_extract_z(const GPDesc* d, int count, int64_t max_n, hipStream_t s);
-// bordered append (k_inc_stream without cell tiles); max_nprod = max over GPs of nprod
-// vf32: the batch's models store V in fp32 (GPDesc::Vf); a batch is of one V precision
-hipError_t launch_inc_factor(const GPDesc* d, int count, int64_t max_nprod, int vf32, hipStream_t s);
 // Descriptors of a batch passed by value as the kernel argument (k_inc_stream_arg,
 // k_inc_lat_arg): a batch step that is one launch then uploads nothing
 constexpr int DESC_ARG_MAX = 8;
@@ -206,6 +203,8 @@ struct DescArg {
   GPDesc d[DESC_ARG_MAX];
 };
 // bordered append + one-pass predict in one launch; max_blocks = max over GPs of nprod + cell tiles
+// (descriptors without cell tiles: the bordered append alone, max_blocks = max over GPs of nprod)
+// vf32: the batch's models store V in fp32 (GPDesc::Vf); a batch is of one V precision
 hipError_t launch_inc_stream(const GPDesc* d, int count, int64_t max_blocks, int vf32, hipStream_t s);
 // the same for ONE GP with its descriptor passed by value (kernel argument): no
 // descriptor upload, and with rows_inline no row copies either

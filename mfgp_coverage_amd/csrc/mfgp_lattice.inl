@@ -110,8 +110,7 @@ __device__ double lat_axis_value(const GPDesc& d, int t, int64_t p, int64_t col)
 __device__ int lattice_xy(const GPDesc& d, double px, double py) {
   const GridLattice& L = d.lat;
   if (L.nx <= 0 || !(px == px) || !(py == py)) return -1;
-  const int ex = (int)rint(fmin(fmax((px - L.x0) * L.xinv, 0.0), (double)(L.nx - 1)));
-  const int ey = (int)rint(fmin(fmax((py - L.y0) * L.yinv, 0.0), (double)(L.ny - 1)));
+  const int ex = lat_round(px, L.x0, L.xinv, L.nx), ey = lat_round(py, L.y0, L.yinv, L.ny);
   int hx = -1, hy = -1;
   for (int t = -1; t <= 1; ++t) {
     const int cx = ex + t, cy = ey + t;
@@ -136,40 +135,6 @@ __device__ __forceinline__ void wait_phase(const GPDesc& d, const unsigned* c, u
   wait_flag(d, c + 1, epoch);
 }
 
-// Rows [lo, n0) of the compact rows are stored: every producer chunk from lo / FCH
-// on holds this launch's epoch, or sync[1] does. Wave 0 polls; bounded.
-__device__ void wait_l21_from(const GPDesc& d, int64_t lo) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    int it = 0;
-    while (true) {
-      bool mine = true;
-      for (int64_t c = lo / FCH + lane; c < d.nprod; c += 64)
-        mine = mine && __hip_atomic_load(d.pflag + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == d.epoch;
-      const bool any = __hip_atomic_load(d.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == d.epoch;
-      if (any || __ballot(!mine) == 0) break;
-      __builtin_amdgcn_s_sleep(MFGP_SPIN_SLEEP);
-      if (++it == (1 << 22)) {
-        if (lane == 0) atomicMin(d.status, SYNC_FAIL);
-        break;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// Spin (this wave) until *f == v; bounded like wait_flag.
-__device__ __forceinline__ void spin_wave(const GPDesc& d, const unsigned* f, unsigned v) {
-  int it = 0;
-  while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != v) {
-    __builtin_amdgcn_s_sleep(MFGP_SPIN_SLEEP);
-    if (++it == (1 << 22)) {
-      if ((threadIdx.x & 63) == 0) atomicMin(d.status, SYNC_FAIL);
-      break;
-    }
-  }
-}
-
 template <class VT>
 __device__ __forceinline__ double l21c_at(const double* l21c, int64_t i, int a) {
   if constexpr (sizeof(VT) == 8) return gp(l21c)[i * KINC + a];
@@ -183,22 +148,10 @@ __device__ __forceinline__ void lat_l22inv(const GPDesc& d, int k, double* L22, 
   const int tid = threadIdx.x;
   for (int e = tid; e < KINC * KINC; e += NT) {
     const double v = ldx<true>(d.l22r + e);
-    L22[e] = (e / KINC < k && e % KINC <= e / KINC) ? v : 0.0;
+    L22[e] = l22r_live(e, k) ? v : 0.0;
   }
   __syncthreads();
-  if (tid < KINC) {
-    // column c of L22^-1 by forward substitution
-    const int c = tid;
-    double x[KINC];
-#pragma unroll
-    for (int i = 0; i < KINC; ++i) {
-      double t = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-      for (int b = 0; b < i; ++b) t -= L22[i * KINC + b] * x[b];
-      x[i] = (i < k && i >= c) ? t / L22[i * KINC + i] : 0.0;
-      Li[i * KINC + c] = x[i];
-    }
-  }
+  l22inv_column(k, L22, Li);
   __syncthreads();
 }
 
@@ -392,8 +345,7 @@ __device__ __forceinline__ void lat_wblock(const GPDesc& d, int64_t u, double* s
       const int a = ar0 + 4 * t;
       const double* p = row_pt(d, n0 + (a < k ? a : 0));
       const double px = p[0], py = p[1];
-      const int ix = (int)rint(fmin(fmax((px - L.x0) * L.xinv, 0.0), (double)(L.nx - 1)));
-      const int iy = (int)rint(fmin(fmax((py - L.y0) * L.yinv, 0.0), (double)(L.ny - 1)));
+      const int ix = lat_round(px, L.x0, L.xinv, L.nx), iy = lat_round(py, L.y0, L.yinv, L.ny);
       cr[t] = (px == px && py == py) ? ix * L.sx + iy * L.sy : 0;
       const dv2 g = reinterpret_cast<const GLOBAL dv2*>(gp(d.grid))[cr[t]];
       miss = miss || (a < k && !(g.x == px && g.y == py));
@@ -686,27 +638,6 @@ __device__ __forceinline__ void lat_wblock(const GPDesc& d, int64_t u, double* s
     __syncthreads();   // Wh is reused by the next block
   }
   if (d.lat_g2) tables_share();
-}
-
-// Wait (wave 0 polls, the workgroup joins at the barrier) until flags f[0, n)
-// all hold the epoch; bounded like wait_flag.
-__device__ void wait_flags_all(const GPDesc& d, const unsigned* f, int64_t n, unsigned epoch) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    int it = 0;
-    while (true) {
-      bool mine = true;
-      for (int64_t i = lane; i < n; i += 64)
-        mine = mine && __hip_atomic_load(f + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch;
-      if (__ballot(!mine) == 0) break;
-      __builtin_amdgcn_s_sleep(MFGP_SPIN_SLEEP);
-      if (++it == (1 << 22)) {
-        if (lane == 0) atomicMin(d.status, SYNC_FAIL);
-        break;
-      }
-    }
-  }
-  __syncthreads();
 }
 
 // Exclusive prefix over the workgroup of NV per-thread counts (in thread order),
@@ -1515,6 +1446,9 @@ __device__ __forceinline__ void lat_epi(const GPDesc& d, int64_t tile, int64_t s
   }
   {
     // the record and the new rows' tables (lat_epi_load, issued by the caller)
+    // (the mask and the column solve below repeat l22r_live / l22inv_column on purpose: calling
+    // either here moved k_inc_lat_arg<16, double, true> from 86 to 140-148 spilled VGPRs;
+    // DESIGN.md section 23)
     using E = LatEpiIn<KA>;
     constexpr int NR = E::NR, NF = E::NF;
     const double(&rv)[NR] = in.rv;
@@ -1982,7 +1916,7 @@ __device__ __forceinline__ void lat_gemm2(const GPDesc& d, int64_t tile) {
   // against 24.13 us. Round 4 had measured the first as noise.)
   auto prologue = [&]() {
   for (int e = tid; e < KINC * KINC + KINC; e += G2NT) {
-    const bool use = e < KINC * KINC ? (e / KINC < k && e % KINC <= e / KINC) : (e - KINC * KINC < k);
+    const bool use = l22r_live(e, k);
     L22[e] = use ? d.l22r[e] : 0.0;
     if (e < KINC * KINC && e / KINC == e % KINC) rdi[e / KINC] = use ? 1.0 / L22[e] : 0.0;
   }

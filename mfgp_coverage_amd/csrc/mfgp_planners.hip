@@ -311,7 +311,7 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
                       (c->fused ? hipSuccess == launch_inc_stream(dd + 2 * it, 1,
                                                                    hd[2 * it].nprod + ntiles_wg(M, hd[2 * it].rsplit, vf),
                                                                    vf, c->stream)
-                                : (hipSuccess == launch_inc_factor(dd + 2 * it, 1, hd[2 * it].nprod, vf, c->stream) &&
+                                : (hipSuccess == launch_inc_stream(dd + 2 * it, 1, hd[2 * it].nprod, vf, c->stream) &&
                                    hipSuccess == launch_vstream(dd + 2 * it + 1, 1, ntiles_wg(M, hd[2 * it + 1].rsplit, vf),
                                                                 vf, c->stream)));
       if (!ok) return run.fail(set_err(MFGP_ERR_DEVICE, "sample_points: launch failed"));

@@ -183,7 +183,7 @@ static int enqueue_inc_factor(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, i
   EvPair ev{};
   int rc = ev_begin(c, ev, 1);
   if (rc) return rc;
-  HIP_TRY(launch_inc_factor(dd, count, max_np, hd[0].vf32, c->stream));
+  HIP_TRY(launch_inc_stream(dd, count, max_np, hd[0].vf32, c->stream));
   return ev_end(c, ev);
 }
 

@@ -767,3 +767,68 @@ def test_capacity_growth_clamped_to_full_predict_limit():
     mu_r, var_r = ref.predict()
     assert np.all(np.isfinite(mu)) and np.all(np.isfinite(var))
     assert _err(mu, var, mu_r, var_r, hyp) < 1e-8
+
+
+# The stream kernels' software ring by regime (k_vstream / k_inc_stream: ring_stream over 8-row
+# stages, four in the ring for the compact rows): n0 = 0 and 8 run the guarded ragged stage or one
+# full stage alone, 23 and 55 the drain (fewer than seven full stages) with a ragged end, 56 and 57
+# the first steady-state pass without and with one, 127 two passes, the drain and a ragged end.
+RING_N0 = [0, 8, 23, 55, 56, 57, 127]
+RING_STEPS = [3, 16, 0]   # compact rows (MODE 2), L21 from A (MODE 1), the re-predict (MODE 0)
+
+
+def _ring_case(n0):
+    """Rows and oracle posteriors of one n0, shared by its four cases: the old rows anywhere in
+    the unit square (a 12 x 12 grid has too few cells for 146 distinct rows), the new ones grid cells."""
+    if n0 not in _ring_case.cache:
+        rng = np.random.default_rng(100 + n0)
+        Xs = _grid(12)
+        X = np.vstack([rng.random((n0, 2)), Xs[rng.choice(Xs.shape[0], sum(RING_STEPS), replace=False)]])
+        y = _field(X, rng)
+        refs, n = [], n0
+        for k in RING_STEPS:
+            n += k
+            refs.append(O.sf_diag(X[:n], y[:n], HYP_SF, Xs))
+        _ring_case.cache[n0] = (Xs, X, y, refs)
+    return _ring_case.cache[n0]
+
+
+_ring_case.cache = {}
+
+
+@pytest.fixture(scope="module")
+def ring_ctx():
+    from mfgp_coverage_amd import _lib
+    c = _lib.Context(0)
+    c.set_lattice(False)   # the one-pass V stream, whatever the batch size
+    return c
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("n0", RING_N0)
+def test_stream_ring_regimes_vs_oracle(ring_ctx, n0, fused, dtype):
+    """SF model on a 12 x 12 grid (M = 144: a ragged second cell workgroup in fp64, a ragged
+    single one in fp32), appends of 3 and 16 rows and a re-predict from every n0 of RING_N0."""
+    from mfgp_coverage_amd import _lib
+    Xs, X, y, refs = _ring_case(n0)
+    f32 = dtype == "f32"
+    kss = O.prior_variance(HYP_SF)
+    ring_ctx.set_fused(fused)
+    m = _lib.Model(ring_ctx, _lib.SF, HYP_SF, 1e-8, dtype=_lib.F32 if f32 else _lib.F64)
+    m.set_grid(Xs)
+    m.set_data(np.empty((0, 2)), np.empty(0), X[:n0], y[:n0])
+    m.predict()
+    n = n0
+    for k, (mu_r, var_r) in zip(RING_STEPS, refs):
+        m.append(X[n:n + k], y[n:n + k])   # (k = 0: drops the kept posterior, so the predict streams again)
+        n += k
+        mu, var = m.predict()
+        e = (O.parity_errors_f32 if f32 else O.parity_errors)(mu, var, mu_r, var_r, kss)
+        print(n0, fused, dtype, k, e)
+        assert max(e) < (O.F32_TOL if f32 else TOL), (k, e)
+    st = m.stats()
+    # the first predict streams too while all n0 rows count as new ones (n0 <= KINC = 16)
+    first_streams = n0 <= 16
+    assert st["inc_factor"] == 2 and st["lattice"] == 0, st
+    assert st["vstream"] == 3 + first_streams and st["full_predict"] == 1 - first_streams, st

@@ -8,8 +8,8 @@ with no acquire. A consumer may then read the data either with a device-scope
 that no workgroup of its XCD read earlier in the launch (L2 and L1 are invalidated
 at the kernel boundary and never filled since), i.e. the first access to it.
 tests/test_codeobj.py checks the polls in the code object; this test checks the
-loads after them in the source: it lists every line of mfgp_lattice.inl and
-mfgp_kernels.hip that names a hand-off buffer -- a GPDesc field below or a local
+loads after them in the source: it lists every line of mfgp_kernels.hip and of the
+.inl files it includes that names a hand-off buffer -- a GPDesc field below or a local
 pointer derived from one -- and classifies it as a store, a pointer derivation,
 an sc1 read (or a poll), or a plain read. Each plain read must be one of the
 audited sites in PLAIN, with the reason it is a first access (or is not a hand-off
@@ -23,10 +23,10 @@ CSRC = os.path.join(ROOT, "mfgp_coverage_amd", "csrc")
 # buffers written in a launch and read by other workgroups of the same launch
 FIELDS = ("l21c", "l22r", "iscr", "wpart", "wv", "zb", "csr", "zvl",
           "pflag", "wflag", "zflag", "sync", "ldone", "wcnt")
-SC1 = ("ldx<true>", "ldx<FUSED>", "ldx<XW>", "__hip_atomic_load", "l21c_ld<", "ldu(", "wait_flag(",
-       "wait_flags_all(", "spin_wave(", "wait_l21(", "wait_l21_from(", "wait_phase(", "__hip_atomic_fetch_add",
+SC1 = ("ldx<true>", "ldx<FUSED>", "ldx<XW>", "__hip_atomic_load", "l21c_ld<", "ldu(", "flag_is(", "wait_flag(",
+       "wait_flags_all(", "spin_wave(", "wait_l21_from(", "wait_phase(", "__hip_atomic_fetch_add",
        "atomicMin(")
-STORE = ("stx<", "st16_wt(", "__hip_atomic_store(", "publish(", "store_l21c<", "arrive_phase(", "st_u(", "st_i(")
+STORE = ("stx<", "st16_wt(", "__hip_atomic_store(", "publish(", "store_l21c<", "inc_row_step<", "arrive_phase(", "st_u(", "st_i(")
 # (file, code snippet) -> why the plain read is a first access (or no hand-off)
 PLAIN = {
     ("mfgp_lattice.inl", ": reinterpret_cast<const VT*>(l21c) + (a < k ? a : 0);"):
@@ -42,18 +42,18 @@ PLAIN = {
         "k_lat_gemm2: the virtual-row lists of the previous launch (kernel boundary)",
     ("mfgp_lattice.inl", "const int64_t j = (lane >> 5) ? vl[1] : vl[0];"):
         "k_lat_gemm2: the virtual-row lists of the previous launch (kernel boundary)",
-    ("mfgp_kernels.hip", "if (ra < k && cb <= ra) v = d.l21c_ok ? d.l22r[e] : d.A[(n0 + cb) * ld + n0 + ra];"):
+    ("mfgp_stream.inl", "if (ra < k && cb <= ra) v = d.l21c_ok ? d.l22r[e] : d.A[(n0 + cb) * ld + n0 + ra];"):
         "V-stream cells: the L22 record after sync[2]; no line of it is read in the launch before that flag",
-    ("mfgp_kernels.hip", "v = d.l21c_ok ? d.l22r[e] : d.zv[n0 + e - KINC * KINC];"):
+    ("mfgp_stream.inl", "v = d.l21c_ok ? d.l22r[e] : d.zv[n0 + e - KINC * KINC];"):
         "V-stream cells: the L22 record after sync[2] (as above)",
-    ("mfgp_kernels.hip", "WsPrefetch pf{(FUSED && mma) ? d.sync + 2 : nullptr, d.epoch, d.l22r, 0u, 0.0, 0.0, false};"):
+    ("mfgp_stream.inl", "return WsPrefetch{on ? d.sync + 2 : nullptr, d.epoch, d.l22r, 0u, 0.0, 0.0, false};"):
         "ws_prefetch polls sync[2] with __hip_atomic_load and reads the L22 record only once it holds the epoch",
-    ("mfgp_kernels.hip", "const WsSrc<2> src{vb, gp(d.l21c) + r, KINC, nullptr, j_hi, j_lo};"):
-        "V stream (fp64): the compact rows, streamed after wait_l21 saw every producer chunk's flag; "
+    ("mfgp_stream.inl", "const WsSrc<2> src{vb, gp(d.l21c) + r, KINC, nullptr, j_hi, j_lo};"):
+        "V stream (fp64): the compact rows, streamed after wait_l21_from saw every producer chunk's flag; "
         "nothing reads them in the launch before",
-    ("mfgp_kernels.hip", "const WfSrc src{vb, reinterpret_cast<const GLOBAL float*>(gp(d.l21c)) + r, nullptr, 0, nullptr, n0};"):
-        "V stream (fp32): the compact rows after wait_l21 (as above)",
-    ("mfgp_kernels.hip", "const double v = d.l22r[e];"):
+    ("mfgp_stream.inl", "const WfSrc src{vb, reinterpret_cast<const GLOBAL float*>(gp(d.l21c)) + r, nullptr, 0, nullptr, n0};"):
+        "V stream (fp32): the compact rows after wait_l21_from (as above)",
+    ("mfgp_stream.inl", "l22r_stage(L22, k, [&](int e, int) { return d.l22r[e]; });"):
         "V-stream epilogue: the L22 record after its sync[2] wait; no line of it is read earlier in the launch",
 }
 
@@ -97,7 +97,7 @@ def classify(path):
 
 def _sites():
     out = []
-    for f in ("mfgp_lattice.inl", "mfgp_kernels.hip"):
+    for f in sorted(n for n in os.listdir(CSRC) if n.endswith(".inl")) + ["mfgp_kernels.hip"]:
         for no, kind, code in classify(os.path.join(CSRC, f)):
             out.append((f, no, kind, code))
     return out

@@ -9,6 +9,8 @@ reads the AMDGPU metadata note (VGPRs, spills, LDS) and counts call
 instructions (s_swappc_b64) in each kernel's disassembly.
 
 usage: python tools/check_codeobj.py mfgp_coverage_amd/libmfgp_hip.so
+       python tools/check_codeobj.py compare OLD.so NEW.so   (two builds, kernel by kernel: a
+       refactor of the kernel sources is checked by the compiler emitting the same code)
 """
 from __future__ import annotations
 
@@ -162,6 +164,50 @@ def kernel_report(path, all_units=False):
     return rep
 
 
+def instruction_streams(path):
+    """{kernel: [(mnemonic, operands, branch target relative to the kernel's start or None)]} of
+    every unit's kernels: what two builds of one source must agree on, wherever the kernels
+    landed in their code objects."""
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for co in code_objects(path, td):
+            for name, ins in disassembly(co).items():
+                base = ins[0][0] if ins else 0
+                # (a branch's operand is its target's address as text: the relative target stands for it)
+                out[name] = [(op, args if t is None else "", None if t is None else t - base) for _, op, args, t in ins]
+    return out
+
+
+RESOURCES = ("vgpr", "agpr", "vgpr_spill", "sgpr_spill", "scratch", "lds")
+
+
+def compare(old, new):
+    """Two builds of the library, kernel by kernel -> {"only_old", "only_new": kernel symbols in one
+    build alone; "code": kernels whose instruction streams differ; "resources": {kernel: {figure:
+    (old, new)}} for the VGPR / AGPR / spill / scratch / LDS figures that differ; "kernels": the
+    number compared}."""
+    ro, rn = kernel_report(old, all_units=True), kernel_report(new, all_units=True)
+    so, sn = instruction_streams(old), instruction_streams(new)
+    both = sorted(set(ro) & set(rn))
+    res = {k: {f: (ro[k][f], rn[k][f]) for f in RESOURCES if ro[k][f] != rn[k][f]} for k in both}
+    return {"only_old": sorted(set(ro) - set(rn)), "only_new": sorted(set(rn) - set(ro)),
+            "code": [k for k in both if so.get(k) != sn.get(k)],
+            "resources": {k: v for k, v in res.items() if v}, "kernels": len(both)}
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "compare":
+        # usage: python tools/check_codeobj.py compare OLD.so NEW.so; exit status 1 if anything differs
+        c = compare(sys.argv[2], sys.argv[3])
+        for key in ("only_old", "only_new"):
+            for k in c[key]:
+                print(f"{key}: {k}")
+        for k in c["code"]:
+            print(f"code differs: {k}")
+        for k, v in c["resources"].items():
+            print(f"resources differ: {k}: " + ", ".join(f"{f} {a} -> {b}" for f, (a, b) in v.items()))
+        same = c["kernels"] - len(set(c["code"]) | set(c["resources"]))
+        print(f"{c['kernels']} kernels compared, {same} identical")
+        sys.exit(1 if c["only_old"] or c["only_new"] or c["code"] or c["resources"] else 0)
     for n, r in sorted(kernel_report(sys.argv[1]).items()):
         print(n, r)
