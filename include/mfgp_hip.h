@@ -388,6 +388,10 @@ int mfgp_debug_read_v(mfgp_model* m, double* v_out, double* vc_out, int64_t n_ma
 /* Tests only: the explicit inverse F = L^-1 that the lattice steps keep, its n = min(current
  * rows, n_max) leading rows and columns as doubles, f_out[i * n + j]; *rows = n (0: none). */
 int mfgp_debug_read_f(mfgp_model* m, double* f_out, int64_t n_max, int64_t* rows);
+/* Tests only: the memory the library holds in this process, out = {device buffers, their
+ * bytes, pinned host buffers, their bytes}; the buffers of the view pool and of views not
+ * yet released count. */
+int mfgp_debug_live(int64_t out[4]);
 /* Copy the lower Cholesky factor L [N,N] (row-major, zeros above the diagonal). */
 int mfgp_get_factor(mfgp_model* m, double* L_out);
 

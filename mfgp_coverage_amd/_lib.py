@@ -47,6 +47,7 @@ SIGNATURES = {
     "mfgp_debug_read_v": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                          _c_int64_p, _c_int64_p]),
     "mfgp_debug_read_f": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_int64_p]),
+    "mfgp_debug_live": (ctypes.c_int, [_c_int64_p]),
     "mfgp_ctx_set_timing_stride": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "mfgp_ctx_set_concurrent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mfgp_batch_append_predict_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -329,6 +330,13 @@ class Context:
 
 _tls = threading.local()
 _default_device = int(os.environ.get("MFGP_DEVICE", "0"))
+
+
+def live_allocations():
+    """Tests only: (device buffers, their bytes, pinned buffers, their bytes) the library holds."""
+    out = (ctypes.c_int64 * 4)()
+    check(lib().mfgp_debug_live(out))
+    return tuple(int(v) for v in out)
 
 
 def set_device(device):

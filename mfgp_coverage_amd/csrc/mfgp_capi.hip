@@ -27,6 +27,8 @@ std::atomic<uint64_t> g_serial{0};
 
 namespace mfgp_host __attribute__((visibility("hidden"))) {
 
+mfgp_own::Live live_dev, live_pin;
+
 int set_err(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -91,24 +93,14 @@ static int drain_timing(mfgp_ctx* c) {
 }
 
 int ensure_h_status(mfgp_ctx* c, size_t n) {
-  if (n <= c->h_status_n) return MFGP_OK;
+  if (sizeof(int) * n <= c->h_status.bytes()) return MFGP_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->h_status) HIP_TRY(hipHostFree(c->h_status));
-  c->h_status = nullptr;
-  c->h_status_n = 0;
-  const size_t want = std::max<size_t>(n, 64);
-  HIP_TRY(hipHostMalloc(&c->h_status, sizeof(int) * want, hipHostMallocDefault));
-  c->h_status_n = want;
-  return MFGP_OK;
+  return pin_alloc(c->h_status, sizeof(int) * std::max<size_t>(n, 64), hipHostMallocDefault);
 }
 
 int ensure_ws(mfgp_ctx* c, size_t bytes) {
-  if (bytes <= c->ws_bytes) return MFGP_OK;
-  const size_t want = std::max(bytes, c->ws_bytes + c->ws_bytes / 2);
-  c->ws_bytes = 0;
-  if (const int rc = renew(c->stream, c->ws, want, false)) return rc;
-  c->ws_bytes = want;
-  return MFGP_OK;
+  if (bytes <= c->ws.bytes()) return MFGP_OK;
+  return dev_alloc(c->ws, c->stream, std::max(bytes, c->ws.bytes() + c->ws.bytes() / 2));
 }
 
 // Grow the training capacity of m to hold `need` rows. Keeps X / y and, when
@@ -123,81 +115,72 @@ int ensure_cap(mfgp_model* m, int64_t need) {
   if (cap > MAX_FULL_CAP && need <= MAX_FULL_CAP) cap = MAX_FULL_CAP;
   int64_t ld = round_up(cap + 1, NB);
   cap = ld - 1;
-  double *X = nullptr, *y = nullptr, *A = nullptr, *Li = nullptr, *zv = nullptr, *isc = nullptr;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMalloc(&X, sizeof(double) * 2 * cap));
-  HIP_TRY(hipMalloc(&y, sizeof(double) * cap));
-  HIP_TRY(hipMalloc(&zv, sizeof(double) * cap));
-  HIP_TRY(hipMalloc(&isc, sizeof(double) * inc_scratch_doubles(cap)));
+  // the new buffers in local owners: a failure anywhere before the swap below frees them
+  // and leaves the model exactly as it was
+  Dev<double> X, y, A, Li, zv, isc, F, tab;
+  Dev<float> Ff;
+  Dev<int> lidx;
+  hipStream_t s = c->stream;
+  int rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  if ((rc = dev_alloc(X, s, sizeof(double) * 2 * cap, A_NO_DRAIN))) return rc;
+  if ((rc = dev_alloc(y, s, sizeof(double) * cap, A_NO_DRAIN))) return rc;
+  if ((rc = dev_alloc(zv, s, sizeof(double) * cap, A_NO_DRAIN))) return rc;
+  if ((rc = dev_alloc(isc, s, sizeof(double) * inc_scratch_doubles(cap), A_NO_DRAIN))) return rc;
   // producer ready flags start below every epoch (epochs are never 0)
-  HIP_TRY(hipMemsetAsync(isc + inc_pflag_offset(cap), 0, sizeof(unsigned) * inc_pflag_count(cap), c->stream));
-  HIP_TRY(hipMalloc(&A, sizeof(double) * ld * ld));
-  HIP_TRY(hipMalloc(&Li, sizeof(double) * (ld / NB) * TILE));
+  HIP_TRY(hipMemsetAsync(isc + inc_pflag_offset(cap), 0, sizeof(unsigned) * inc_pflag_count(cap), s));
+  if ((rc = dev_alloc(A, s, sizeof(double) * ld * ld, A_NO_DRAIN))) return rc;
+  if ((rc = dev_alloc(Li, s, sizeof(double) * (ld / NB) * TILE, A_NO_DRAIN))) return rc;
   const int64_t n = m->NL + m->NH;
   if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(X, m->X, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(y, m->y, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(X, m->X, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(y, m->y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
   }
   const bool keep = m->A && m->factored && m->ablk > 0;
   if (keep) {
     HIP_TRY(hipMemcpy2DAsync(A, sizeof(double) * ld, m->A, sizeof(double) * m->ld, sizeof(double) * m->ld, m->ld,
-                             hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(Li, m->Linv, sizeof(double) * (m->ld / NB) * TILE, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(zv, m->zv, sizeof(double) * m->cap, hipMemcpyDeviceToDevice, c->stream));
+                             hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(Li, m->Linv, sizeof(double) * (m->ld / NB) * TILE, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(zv, m->zv, sizeof(double) * m->cap, hipMemcpyDeviceToDevice, s));
   }
   // the lattice step's F and tables move to the new leading dimension too
-  double *F = nullptr, *tab = nullptr;
-  float* Ff = nullptr;
-  int* lidx = nullptr;
   if (keep && m->F && m->F_n > 0) {
-    HIP_TRY(hipMalloc(&F, sizeof(double) * fblk_size(ld)));
-    HIP_TRY(hipMemsetAsync(F, 0, sizeof(double) * fblk_size(ld), c->stream));
+    if ((rc = dev_alloc(F, s, sizeof(double) * fblk_size(ld), A_ZERO | A_NO_DRAIN))) return rc;
     for (int64_t jb = 0; 64 * jb < m->F_n; ++jb)   // each column block's rows [64 jb, F_n)
       HIP_TRY(hipMemcpyAsync(F + fblk_off(jb, ld), m->F + fblk_off(jb, m->F_ld),
-                             sizeof(double) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, c->stream));
+                             sizeof(double) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
     if (m->Ff) {   // (MFGP_F32: the rows past the build live in Ff only)
-      HIP_TRY(hipMalloc(&Ff, sizeof(float) * fblk_size(ld)));
-      HIP_TRY(hipMemsetAsync(Ff, 0, sizeof(float) * fblk_size(ld), c->stream));
+      if ((rc = dev_alloc(Ff, s, sizeof(float) * fblk_size(ld), A_ZERO | A_NO_DRAIN))) return rc;
       for (int64_t jb = 0; 64 * jb < m->F_n; ++jb)
         HIP_TRY(hipMemcpyAsync(Ff + fblk_off(jb, ld), m->Ff + fblk_off(jb, m->F_ld),
-                               sizeof(float) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, c->stream));
+                               sizeof(float) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
     }
   }
   if (m->tab && m->tab_n > 0) {
-    HIP_TRY(hipMalloc(&tab, sizeof(double) * 4 * ld * m->tabw));
-    HIP_TRY(hipMemsetAsync(tab, 0, sizeof(double) * 4 * ld * m->tabw, c->stream));
+    if ((rc = dev_alloc(tab, s, sizeof(double) * 4 * ld * m->tabw, A_ZERO | A_NO_DRAIN))) return rc;
     for (int t = 0; t < 4; ++t)
       HIP_TRY(hipMemcpyAsync(tab + (size_t)t * ld * m->tabw, m->tab + (size_t)t * m->tab_ld * m->tabw,
-                             sizeof(double) * m->tab_n * m->tabw, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMalloc(&lidx, sizeof(int) * ld));
-    HIP_TRY(hipMemcpyAsync(lidx, m->lidx, sizeof(int) * m->tab_n, hipMemcpyDeviceToDevice, c->stream));
+                             sizeof(double) * m->tab_n * m->tabw, hipMemcpyDeviceToDevice, s));
+    if ((rc = dev_alloc(lidx, s, sizeof(int) * ld, A_NO_DRAIN))) return rc;
+    HIP_TRY(hipMemcpyAsync(lidx, m->lidx, sizeof(int) * m->tab_n, hipMemcpyDeviceToDevice, s));
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (m->F) HIP_TRY(hipFree(m->F));
-  if (m->Ff) HIP_TRY(hipFree(m->Ff));
-  if (m->tab) HIP_TRY(hipFree(m->tab));
-  if (m->lidx) HIP_TRY(hipFree(m->lidx));
-  m->lidx = lidx;
-  m->F = F;
-  m->Ff = Ff;
-  m->F_ld = F ? ld : 0;
-  if (!F) m->F_n = 0;
-  m->tab = tab;
-  m->tab_ld = tab ? ld : 0;
-  if (!tab) m->tab_n = 0;
-  if (m->X) HIP_TRY(hipFree(m->X));
-  if (m->y) HIP_TRY(hipFree(m->y));
-  if (m->A) HIP_TRY(hipFree(m->A));
-  if (m->Linv) HIP_TRY(hipFree(m->Linv));
-  if (m->zv) HIP_TRY(hipFree(m->zv));
-  if (m->iscr) HIP_TRY(hipFree(m->iscr));
-  m->iscr = isc;
+  HIP_TRY(hipStreamSynchronize(s));
+  // the commit: nothing below fails; the locals leave with the old buffers and free them
+  m->lidx.swap(lidx);
+  m->F.swap(F);
+  m->Ff.swap(Ff);
+  m->F_ld = m->F ? ld : 0;
+  if (!m->F) m->F_n = 0;
+  m->tab.swap(tab);
+  m->tab_ld = m->tab ? ld : 0;
+  if (!m->tab) m->tab_n = 0;
+  m->X.swap(X);
+  m->y.swap(y);
+  m->A.swap(A);
+  m->Linv.swap(Li);
+  m->zv.swap(zv);
+  m->iscr.swap(isc);
   m->l21c_N = -1;
-  m->X = X;
-  m->y = y;
-  m->A = A;
-  m->Linv = Li;
-  m->zv = zv;
   m->cap = cap;
   m->ld = ld;
   if (!keep) {
@@ -214,27 +197,27 @@ static size_t v_elem(const mfgp_model* m) { return m->dtype == MFGP_F32 ? sizeof
 int ensure_v(mfgp_model* m) {
   const int64_t vld = round_up(m->cap, PRB);
   const int64_t tiles = ntiles_grid(m->M);
-  if (m->V && m->vld == vld && m->vtiles >= tiles) return MFGP_OK;
+  if (m->V && m->tred && m->vld == vld && m->vtiles >= tiles) return MFGP_OK;
   hipStream_t s = m->ctx->stream;
   const size_t es = v_elem(m);
-  void* V = nullptr;
-  HIP_TRY(hipMalloc(&V, es * (size_t)tiles * vld * PBM));
-  if (m->V && m->v_n > 0 && m->vtiles >= tiles && m->vld >= m->v_n) {
-    // capacity grew: move the valid rows of every tile to the new row stride
+  int rc;
+  Dev<void> V;   // committed once the valid rows are in it: until then the model keeps its own
+  if ((rc = dev_alloc(V, s, es * (size_t)tiles * vld * PBM, A_NO_DRAIN))) return rc;
+  const bool moved = m->V && m->v_n > 0 && m->vtiles >= tiles && m->vld >= m->v_n;
+  if (moved)   // capacity grew: move the valid rows of every tile to the new row stride
     HIP_TRY(hipMemcpy2DAsync(V, es * vld * PBM, m->V, es * m->vld * PBM, es * m->v_n * PBM, tiles,
                              hipMemcpyDeviceToDevice, s));
-  } else {
-    m->v_n = 0;
-  }
   HIP_TRY(hipStreamSynchronize(s));
-  if (m->V) HIP_TRY(hipFree(m->V));
-  m->V = V;
+  if (!moved) m->v_n = 0;
+  m->V.swap(V);
+  V.reset();
   m->vld = vld;
   if (tiles > m->vtiles || !m->tred) {
     // [arrival counter | (max, argmax) per 64-cell tile (k_predict) or per 32-cell
     // wave group (one-pass predicts)]; the counter is zero between launches (the
     // last arriver of each launch resets it)
-    if (const int rc = renew(s, m->tred, sizeof(double) * (4 * tiles + 1), true)) return rc;
+    m->tred_n = 0;
+    if ((rc = dev_alloc(m->tred, s, sizeof(double) * (4 * tiles + 1), A_ZERO))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     m->tred_n = 4 * tiles + 1;
   }
@@ -257,8 +240,8 @@ void fill_desc(GPDesc& d, mfgp_model* m) {
   d.Linv = m->Linv;
   d.grid = m->grid;
   d.lat = m->lat;
-  d.V = m->dtype == MFGP_F64 ? static_cast<double*>(m->V) : nullptr;
-  d.Vf = m->dtype == MFGP_F32 ? static_cast<float*>(m->V) : nullptr;
+  d.V = m->dtype == MFGP_F64 ? static_cast<double*>(m->V.get()) : nullptr;
+  d.Vf = m->dtype == MFGP_F32 ? static_cast<float*>(m->V.get()) : nullptr;
   d.vf32 = m->dtype == MFGP_F32 ? 1 : 0;
   d.zv = m->zv;
   d.iscr = m->iscr;
@@ -286,7 +269,7 @@ static int ensure_res(mfgp_model* m) {
   if (m->res && m->res_M >= m->M) return MFGP_OK;
   m->res_M = 0;
   m->res_n[0] = m->res_n[1] = -1;
-  if (const int rc = renew(m->ctx->stream, m->res, sizeof(double) * 4 * (size_t)m->M, false)) return rc;
+  if (const int rc = dev_alloc(m->res, m->ctx->stream, sizeof(double) * 4 * (size_t)m->M)) return rc;
   m->res_M = m->M;
   return MFGP_OK;
 }
@@ -326,41 +309,48 @@ int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu) {
   const int64_t ld = m->ld, tabw = lat_tabw(m);
   const bool ff = m->dtype == MFGP_F32;   // (F streamed in fp32: DESIGN.md section 2.3)
   int rc;
+  // Each group: the extent it is keyed by reset with the buffers (free-then-allocate: F, the
+  // tables and their kin never exist twice), set again once all of the group are there. A
+  // refused allocation leaves the group empty behind an extent that makes the next call
+  // allocate again.
   if (!m->F || m->F_ld != ld || (ff && !m->Ff)) {
-    if ((rc = renew(s, m->F, sizeof(double) * fblk_size(ld), true))) return rc;   // F's upper triangle stays zero
-    if (m->Ff) HIP_TRY(hipFree(m->Ff));
-    m->Ff = nullptr;
-    if (ff && (rc = renew(s, m->Ff, sizeof(float) * fblk_size(ld), true))) return rc;
+    m->F_ld = m->F_n = 0;
+    if ((rc = dev_alloc(m->F, s, sizeof(double) * fblk_size(ld), A_ZERO))) return rc;   // F's upper triangle stays zero
+    m->Ff.reset();
+    if (ff && (rc = dev_alloc(m->Ff, s, sizeof(float) * fblk_size(ld), A_ZERO))) return rc;
     m->F_ld = ld;
-    m->F_n = 0;
   }
   if (!m->tab || m->tab_ld != ld || m->tabw != tabw) {
-    if ((rc = renew(s, m->tab, sizeof(double) * 4 * ld * tabw, true))) return rc;
-    if ((rc = renew(s, m->lidx, sizeof(int) * ld, false))) return rc;
+    m->tab_ld = m->tabw = m->tab_n = 0;
+    if ((rc = dev_alloc(m->tab, s, sizeof(double) * 4 * ld * tabw, A_ZERO))) return rc;
+    if ((rc = dev_alloc(m->lidx, s, sizeof(int) * ld))) return rc;
     m->tab_ld = ld;
     m->tabw = tabw;
-    m->tab_n = 0;
   }
   if (!m->wv || m->wv_ld != ld) {
-    if ((rc = renew(s, m->wv, sizeof(double) * ld * KINC, true))) return rc;
-    if ((rc = renew(s, m->wflag, sizeof(unsigned) * (ld / 64 + 2), true))) return rc;   // below every epoch
-    if ((rc = renew(s, m->wcnt, sizeof(unsigned) * 2 * (ld / 64 + 2), true))) return rc;
-    if ((rc = renew(s, m->wpart, sizeof(double) * 1024 * (LAT_WU_MAX + ld / 64 + 1), false))) return rc;
+    m->wv_ld = 0;
+    if ((rc = dev_alloc(m->wv, s, sizeof(double) * ld * KINC, A_ZERO))) return rc;
+    if ((rc = dev_alloc(m->wflag, s, sizeof(unsigned) * (ld / 64 + 2), A_ZERO))) return rc;   // below every epoch
+    if ((rc = dev_alloc(m->wcnt, s, sizeof(unsigned) * 2 * (ld / 64 + 2), A_ZERO))) return rc;
+    if ((rc = dev_alloc(m->wpart, s, sizeof(double) * 1024 * (LAT_WU_MAX + ld / 64 + 1)))) return rc;
     m->wv_ld = ld;
   }
   if (m->gcnt_n != tiles) {
     // [tiles] arrival counters of the splits | [tiles] flags (the epoch once all arrived)
-    if ((rc = renew(s, m->gcnt, sizeof(unsigned) * 2 * tiles, true))) return rc;   // flags below every epoch
+    m->gcnt_n = 0;
+    if ((rc = dev_alloc(m->gcnt, s, sizeof(unsigned) * 2 * tiles, A_ZERO))) return rc;   // flags below every epoch
     m->gcnt_n = tiles;
   }
   // the fused var max / argmax: one (max, argmax) slot per GEMM workgroup
   if (m->tred && 2 * tiles * ksplit + 1 > m->tred_n) {
     const int64_t nd = 2 * tiles * ksplit + 1;
-    if ((rc = renew(s, m->tred, sizeof(double) * nd, true))) return rc;
+    m->tred_n = 0;   // (a refused tred: ensure_v allocates it again)
+    if ((rc = dev_alloc(m->tred, s, sizeof(double) * nd, A_ZERO))) return rc;
     m->tred_n = nd;
   }
   if (!m->axt || m->axt_w != tabw) {
-    if ((rc = renew(s, m->axt, sizeof(double) * 4 * (tabw + 1) * tabw, false, true))) return rc;
+    m->axt_w = 0;
+    if ((rc = dev_alloc(m->axt, s, sizeof(double) * 4 * (tabw + 1) * tabw, A_2M))) return rc;
     m->axt_w = tabw;
     m->axt_gen = UINT64_MAX;   // build before use
   }
@@ -368,24 +358,26 @@ int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu) {
   // that could lie off the lattice; zeros where never written (padding rows)
   const int64_t zrows = round_up(m->lat.ny, ZKS) + ld;
   if (!m->zb || m->zb_rows != zrows || m->zb_w != tabw || m->zb_ka < ka) {
-    if ((rc = renew(s, m->zb, sizeof(double) * 2 * zrows * tabw * ka, true))) return rc;
-    if ((rc = renew(s, m->zvl, sizeof(int) * 2 * (zrows + 1), true))) return rc;
+    m->zb_rows = m->zb_w = 0;
+    m->zb_ka = 0;
+    if ((rc = dev_alloc(m->zb, s, sizeof(double) * 2 * zrows * tabw * ka, A_ZERO))) return rc;
+    if ((rc = dev_alloc(m->zvl, s, sizeof(int) * 2 * (zrows + 1), A_ZERO))) return rc;
     m->zb_rows = zrows;
     m->zb_w = tabw;
     m->zb_ka = ka;
   }
-  if (m->csr_n < csr_bytes(tabw, ld)) {
-    m->csr_n = csr_bytes(tabw, ld);
-    if ((rc = renew(s, m->csr, m->csr_n, false, true))) return rc;
-  }
-  if (!m->ldone && (rc = renew(s, m->ldone, sizeof(unsigned) * 4, true))) return rc;   // no arrivals; flags below every epoch
+  // (the member lists' extent is the owner's own: empty reads as 0 bytes)
+  if ((int64_t)m->csr.bytes() < csr_bytes(tabw, ld) && (rc = dev_alloc(m->csr, s, csr_bytes(tabw, ld), A_2M))) return rc;
+  if (!m->ldone && (rc = dev_alloc(m->ldone, s, sizeof(unsigned) * 4, A_ZERO))) return rc;   // no arrivals; flags below every epoch
   if (m->zflag_n < nzu + 2) {
-    if ((rc = renew(s, m->zflag, sizeof(unsigned) * (nzu + 2), true))) return rc;   // below every epoch
+    m->zflag_n = 0;
+    if ((rc = dev_alloc(m->zflag, s, sizeof(unsigned) * (nzu + 2), A_ZERO))) return rc;   // below every epoch
     m->zflag_n = (nzu + 2);
   }
   const size_t need = ksplit > 1 ? (size_t)tiles * ksplit * 8192 : 0;   // LAT_PART doubles per split tile
   if (need > m->gpart_n) {
-    if ((rc = renew(s, m->gpart, sizeof(double) * need, false))) return rc;
+    m->gpart_n = 0;
+    if ((rc = dev_alloc(m->gpart, s, sizeof(double) * need))) return rc;
     m->gpart_n = need;
   }
   return MFGP_OK;
@@ -407,9 +399,9 @@ int ensure_vcol(mfgp_model* m) {
   // rows of the old store that stay valid at the new stride (the same grid and generation)
   const int64_t keep =
       (m->Vc && m->vc_gen == m->gen && m->vc_M == M) ? std::min({m->vc_n, m->v_n, ldc, m->vc_ld}) : 0;
-  void* const old = m->Vc;
+  Dev<void> old;   // the old store until its kept rows are copied (freed on every return)
+  old.swap(m->Vc);
   const int64_t old_ld = m->vc_ld;
-  m->Vc = nullptr;
   m->vc_n = 0;
   m->vc_ld = m->vc_M = 0;
   const size_t es = v_elem(m);
@@ -417,17 +409,14 @@ int ensure_vcol(mfgp_model* m) {
   size_t free_b = 0, total_b = 0;
   bool ok = c->lat_vcol != 0 && ldc > 0 && M > 0 && m->V && bytes <= budget;
   if (ok && hipMemGetInfo(&free_b, &total_b) == hipSuccess) ok = (size_t)bytes <= free_b / 4;
-  if (ok && hipMalloc(&m->Vc, (size_t)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    m->Vc = nullptr;
-    ok = false;
-  }
+  if (ok && dev_alloc(m->Vc, c->stream, (size_t)bytes, A_NO_DRAIN) != MFGP_OK) ok = false;   // (refused: no store)
   if (ok && old && keep > 0) {
+    // (a failed copy: the new store with no valid rows, vc_ld == 0, so the next call starts over)
     HIP_TRY(hipMemcpy2DAsync(m->Vc, es * ldc, old, es * old_ld, es * keep, M, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     m->vc_n = keep;
   }
-  if (old) HIP_TRY(hipFree(old));
+  old.reset();
   if (!ok) {
     m->vc_deny_ld = ldc;
     m->vc_deny_M = M;
@@ -442,13 +431,6 @@ int ensure_vcol(mfgp_model* m) {
 int64_t vcol_rows(const mfgp_model* m) {
   return (m->Vc && m->vc_gen == m->gen && m->vc_ld == m->vld && m->vc_M == m->M) ? std::min(m->vc_n, m->v_n) : 0;
 }
-static void free_lat(mfgp_model* m) {
-  for (void* p : {(void*)m->csr, (void*)m->F, (void*)m->Ff, (void*)m->tab, (void*)m->wv, (void*)m->wflag,
-                  (void*)m->wcnt, (void*)m->wpart, (void*)m->gpart, (void*)m->gcnt, (void*)m->res, (void*)m->lidx,
-                  (void*)m->axt, (void*)m->zb, (void*)m->zflag, (void*)m->ldone, (void*)m->zvl, m->Vc})
-    if (p) (void)hipFree(p);
-}
-
 int status_error(int st) {
   if (st == INT_MIN)   // wait_flag gave up (mfgp_kernels.hip): a hand-off inside k_inc_stream never arrived
     return set_err(MFGP_ERR_DEVICE, "device synchronisation timeout in the fused append+predict launch");
@@ -474,9 +456,11 @@ int read_status(mfgp_model* m) {
 // the size it needs before it allocates. Bounded: beyond VIEW_POOL_MAX the
 // returned buffer is freed.
 struct ViewBuf {
-  double* host;
+  double* host;  // released by its owner (a model's spec_out); adopted again by owner() below
   int64_t cap;   // doubles per half ([2][cap]), then the trailer (max var, argmax) at [2 cap]
   int has_max;   // the trailer holds the fused max / argmax of the var half
+  static size_t bytes(int64_t cap) { return sizeof(double) * (2 * (size_t)cap + 2); }
+  Pin<double> owner() const { return Pin<double>(host, bytes(cap)); }
 };
 static std::mutex g_view_mu;
 static std::vector<ViewBuf> g_view_pool;
@@ -486,12 +470,12 @@ int ensure_spec_out(mfgp_model* m) {
   if (m->spec_out && m->spec_cap >= m->M) return MFGP_OK;
   mfgp_ctx* c = m->ctx;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (m->spec_out) HIP_TRY(hipHostFree(m->spec_out));
-  m->spec_out = nullptr;
+  m->spec_out.reset();
   m->spec_out_dev = nullptr;
   m->spec_cap = 0;
   m->spec_valid = false;
   m->spec_max = false;
+  int64_t cap = m->M;
   {
     // best fit: the smallest pooled buffer that holds M (a small model does not take
     // the large buffer another model just returned)
@@ -502,24 +486,20 @@ int ensure_spec_out(mfgp_model* m) {
         best = i;
     if (best < g_view_pool.size()) {
       // (the pool's buffers are laid out [2][cap]: mu at 0, var at cap)
-      m->spec_out = g_view_pool[best].host;
-      m->spec_cap = g_view_pool[best].cap;
+      m->spec_out = g_view_pool[best].owner();
+      cap = g_view_pool[best].cap;
       g_view_pool.erase(g_view_pool.begin() + (long)best);
     }
   }
-  if (m->spec_out) {
-    void* dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dev, m->spec_out, 0));
-    m->spec_out_dev = static_cast<double*>(dev);
-    return MFGP_OK;
-  }
+  int rc;
   // portable: a pooled buffer may serve a model of a context on another device
-  HIP_TRY(hipHostMalloc(&m->spec_out, sizeof(double) * (2 * (size_t)m->M + 2),
-                        hipHostMallocMapped | hipHostMallocPortable));
-  void* dev = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&dev, m->spec_out, 0));
-  m->spec_out_dev = static_cast<double*>(dev);
-  m->spec_cap = m->M;
+  if (!m->spec_out && (rc = pin_alloc(m->spec_out, ViewBuf::bytes(cap), hipHostMallocMapped | hipHostMallocPortable)))
+    return rc;
+  if ((rc = pin_device(m->spec_out, m->spec_out_dev))) {
+    m->spec_out.reset();
+    return rc;
+  }
+  m->spec_cap = cap;   // (with the buffer and its device address there)
   return MFGP_OK;
 }
 
@@ -647,8 +627,9 @@ int mfgp_ctx_create(int device, mfgp_ctx** out) {
     c->lattice = v != 0;
     c->lat_force = v == 2;
   }
-  HIP_TRY(hipHostMalloc(&c->h_ring, sizeof(GPDesc) * RING * MAXB, hipHostMallocDefault));
-  HIP_TRY(hipMalloc(&c->d_ring, sizeof(GPDesc) * RING * MAXB));
+  int rc;
+  if ((rc = pin_alloc(c->h_ring, sizeof(GPDesc) * RING * MAXB, hipHostMallocDefault))) return rc;
+  if ((rc = dev_alloc(c->d_ring, c->stream, sizeof(GPDesc) * RING * MAXB, A_NO_DRAIN))) return rc;
   for (int i = 0; i < RING; ++i) {
     HIP_TRY(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
     c->ring_used[i] = false;
@@ -665,14 +646,8 @@ void mfgp_ctx_destroy(mfgp_ctx* c) {
   (void)drain_timing(c);
   for (auto e : c->pool) (void)hipEventDestroy(e);
   for (int i = 0; i < RING; ++i) (void)hipEventDestroy(c->ring_ev[i]);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->vscr) (void)hipFree(c->vscr);
-  (void)free_nlml_scratch(c);
-  if (c->d_ring) (void)hipFree(c->d_ring);
-  if (c->h_status) (void)hipHostFree(c->h_status);
-  if (c->h_ring) (void)hipHostFree(c->h_ring);
   if (c->own) (void)hipStreamDestroy(c->own);
-  delete c;
+  delete c;   // (its buffers free themselves)
 }
 
 int mfgp_ctx_trim(mfgp_ctx* c) {
@@ -680,13 +655,11 @@ int mfgp_ctx_trim(mfgp_ctx* c) {
   if (const int rc_ = settle(c)) return rc_;
   if (!c) return set_err(MFGP_ERR_ARG, "null ctx");
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->vscr) HIP_TRY(hipFree(c->vscr));
-  c->vscr = nullptr;
-  c->vscr_bytes = 0;
-  if (c->ws) HIP_TRY(hipFree(c->ws));
-  c->ws = nullptr;
-  c->ws_bytes = 0;
-  return free_nlml_scratch(c);
+  c->vscr.reset();
+  c->ws.reset();
+  c->nb_dev.reset();
+  c->nb_host.reset();
+  return MFGP_OK;
 }
 
 // A switch of the context changes between launches: the context checked, a running
@@ -859,7 +832,8 @@ int mfgp_model_create(mfgp_ctx* c, int kind, int dtype, const double* hyp, int n
   const int want = kind == MFGP_SF ? 4 : 9;
   if (!hyp || nhyp != want)
     return set_err(MFGP_ERR_ARG, "Hyperparameters must be of length 4 (single-fidelity) or 9 (multi-fidelity)");
-  mfgp_model* m = new mfgp_model();
+  ModelGuard guard(new mfgp_model());   // until *out is set, every failing return destroys it
+  mfgp_model* m = guard.get();
   m->ctx = c;
   m->kind = kind;
   m->dtype = dtype;
@@ -867,19 +841,16 @@ int mfgp_model_create(mfgp_ctx* c, int kind, int dtype, const double* hyp, int n
   std::memcpy(m->hyp, hyp, sizeof(double) * nhyp);
   m->jitter = jitter;
   bump_serial(m);
-  HIP_TRY(hipMalloc(&m->status, sizeof(int)));
+  int rc;
+  if ((rc = dev_alloc(m->status, c->stream, sizeof(int), A_NO_DRAIN))) return rc;
   {
     // "no failure" until a step writes it: a step whose kernels all skip (a gated
     // model of mfgp_batch_sample_points) must not read an uninitialised word
     const int ok = INT_MAX;
     HIP_TRY(hipMemcpy(m->status, &ok, sizeof(int), hipMemcpyHostToDevice));
   }
-  int rc = ensure_cap(m, 63);
-  if (rc) {
-    mfgp_model_destroy(m);
-    return rc;
-  }
-  *out = m;
+  if ((rc = ensure_cap(m, 63))) return rc;
+  *out = guard.release();
   return MFGP_OK;
 }
 
@@ -894,24 +865,7 @@ void mfgp_model_destroy(mfgp_model* m) {
     as.erase(std::remove_if(as.begin(), as.end(), [m](const mfgp_ctx::AsyncStatus& e) { return e.m == m; }),
              as.end());
   }
-  if (m->spec_out) (void)hipHostFree(m->spec_out);
-  if (m->status_host) (void)hipHostFree(m->status_host);
-  for (void* p : {(void*)m->X, (void*)m->y, (void*)m->A, (void*)m->Linv, (void*)m->zv, (void*)m->iscr,
-                  (void*)m->status, (void*)m->grid, m->V, (void*)m->tred, (void*)m->sync})
-    if (p) (void)hipFree(p);
-  if (m->look) {
-    if (m->look->W) (void)hipFree(m->look->W);
-    if (m->look->L22) (void)hipFree(m->look->L22);
-    if (m->look->pfid) (void)hipFree(m->look->pfid);
-    delete m->look;
-  }
-  if (m->samp) {
-    if (m->samp->fac) (void)hipFree(m->samp->fac);
-    if (m->samp->lidx) (void)hipFree(m->samp->lidx);
-    delete m->samp;
-  }
-  free_lat(m);
-  delete m;
+  delete m;   // (its buffers and records free themselves)
 }
 
 int mfgp_ctx_planner_stats(mfgp_ctx* c, int64_t* out, int n, int reset) {
@@ -931,10 +885,8 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
   mfgp_ctx* c = src->ctx;
   mfgp_model* m = nullptr;
   if ((rc = mfgp_model_create(c, src->kind, src->dtype, src->hyp, src->nhyp, src->jitter, &m))) return rc;
-  if ((rc = ensure_cap(m, src->cap))) {
-    mfgp_model_destroy(m);
-    return rc;
-  }
+  ModelGuard guard(m);   // until *out is set, every failing return destroys the copy
+  if ((rc = ensure_cap(m, src->cap))) return rc;
   // same capacity => same ld: the factor copies verbatim
   const int64_t n = src->NL + src->NH;
   m->NL = src->NL;
@@ -955,7 +907,7 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
     m->factor_jitter = src->factor_jitter;
   }
   if (src->M > 0) {
-    HIP_TRY(hipMalloc(&m->grid, sizeof(double) * 2 * src->M));
+    if ((rc = dev_alloc(m->grid, c->stream, sizeof(double) * 2 * src->M, A_NO_DRAIN))) return rc;
     HIP_TRY(hipMemcpyAsync(m->grid, src->grid, sizeof(double) * 2 * src->M, hipMemcpyDeviceToDevice, c->stream));
     m->M = m->Mcap = src->M;
     m->lat = src->lat;
@@ -970,7 +922,7 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
     }
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
-  *out = m;
+  *out = guard.release();
   return MFGP_OK;
 }
 
@@ -1038,29 +990,44 @@ int mfgp_set_grid(mfgp_model* m, const double* xs, int64_t M) {
   if (rc) return rc;
   if (M < 0 || (M > 0 && !xs)) return set_err(MFGP_ERR_ARG, "bad grid");
   mfgp_ctx* c = m->ctx;
-  m->v_n = 0;   // V columns belong to the previous grid
-  m->spec_valid = false;
-  m->gen += 1;
-  bump_serial(m);
-  if (M > m->Mcap) {
-    if ((rc = renew(c->stream, m->grid, sizeof(double) * 2 * M, false))) return rc;
+  // The new grid goes to the device first: into a buffer of its own where the model's is
+  // too small, so that a refused allocation or a failed copy leaves the model on its old
+  // grid, untouched. Where it fits, the copy overwrites the old grid in place: that one is
+  // gone first, and a failed copy leaves a model without a grid (M == 0).
+  Dev<double> grown;
+  if (M > m->Mcap && (rc = dev_alloc(grown, c->stream, sizeof(double) * 2 * M))) return rc;
+  auto old_grid_gone = [m] {
+    m->M = 0;
+    m->v_n = 0;   // V columns belong to the previous grid
+    m->spec_valid = false;
+    m->gen += 1;
+    bump_serial(m);
+    m->lat = GridLattice{};
+    m->hax.clear();
+    m->hay.clear();
+  };
+  if (!grown) old_grid_gone();
+  double* const g = grown ? grown.get() : m->grid.get();
+  std::vector<double> h(2 * (size_t)M);
+  if (M > 0) {
+    HIP_TRY(hipMemcpyAsync(g, xs, sizeof(double) * 2 * M, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(h.data(), g, sizeof(double) * 2 * M, hipMemcpyDeviceToHost));
+  } else {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  if (grown) {
+    old_grid_gone();
+    m->grid.swap(grown);
     m->Mcap = M;
   }
   m->M = M;
-  if (M > 0) HIP_TRY(hipMemcpyAsync(m->grid, xs, sizeof(double) * 2 * M, hipMemcpyDefault, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  m->lat = GridLattice{};
   if (M > 0) {
-    std::vector<double> h(2 * (size_t)M);
-    HIP_TRY(hipMemcpy(h.data(), m->grid, sizeof(double) * 2 * M, hipMemcpyDeviceToHost));
     m->lat = detect_lattice(h.data(), M);
     m->hax.assign((size_t)std::max(m->lat.nx, 0), 0.0);
     m->hay.assign((size_t)std::max(m->lat.ny, 0), 0.0);
     for (int i = 0; i < m->lat.nx; ++i) m->hax[i] = h[2 * (i * m->lat.sx)];
     for (int i = 0; i < m->lat.ny; ++i) m->hay[i] = h[2 * (i * m->lat.sy) + 1];
-  } else {
-    m->hax.clear();
-    m->hay.clear();
   }
   return MFGP_OK;
 }
@@ -1072,9 +1039,9 @@ int mfgp_set_data(mfgp_model* m, const double* XL, const double* yL, int64_t NL,
   if (rc) return rc;
   if (NL < 0 || NH < 0) return set_err(MFGP_ERR_ARG, "negative sizes");
   if (m->kind == MFGP_SF && NL != 0) return set_err(MFGP_ERR_ARG, "SF model takes its data in the H slots");
+  if ((rc = ensure_cap(m, NL + NH))) return rc;   // (refused: the model, its serial and kept result as they were)
   m->spec_valid = false;
   bump_serial(m);
-  if ((rc = ensure_cap(m, NL + NH))) return rc;
   m->NL = NL;
   m->NH = NH;
   if ((rc = copy_rows(m, 0, XL, yL, NL))) return rc;
@@ -1089,12 +1056,12 @@ int mfgp_append(mfgp_model* m, const double* X, const double* y, int64_t k) {
   int rc = entry.rc;
   if (rc) return rc;
   if (k < 0) return set_err(MFGP_ERR_ARG, "negative k");
+  const int64_t n = m->NL + m->NH;
+  if ((rc = ensure_cap(m, n + k))) return rc;   // (refused: the model, its serial and kept result as they were)
   m->spec_valid = false;
   if (k > 0) bump_serial(m);
   const bool spec = m->pred_since_append;   // the last append was followed by a predict
   m->pred_since_append = false;
-  const int64_t n = m->NL + m->NH;
-  if ((rc = ensure_cap(m, n + k))) return rc;
   if (k > 0 && (!X || !y)) return set_err(MFGP_ERR_ARG, "null data pointer with k=%lld", (long long)k);
   m->NH += k;
   if (!m->ctx->incremental) m->factored = false;   // reference behaviour: refactor from scratch
@@ -1153,12 +1120,11 @@ static int predict_view(mfgp_model* m, double** mu, double** var, void** view, i
     // the predict's host outputs are the result buffer itself: no copy
     if ((rc = mfgp_predict(m, m->spec_out, m->spec_out + m->spec_cap))) return rc;
   }
-  ViewBuf* v = new ViewBuf{m->spec_out, m->spec_cap, m->spec_max ? 1 : 0};
-  *mu = m->spec_out;
-  *var = m->spec_out + m->spec_cap;
-  *view = v;
   // the buffer is the caller's now: the model's next host-bound predict takes another
-  m->spec_out = nullptr;
+  ViewBuf* v = new ViewBuf{m->spec_out.release(), m->spec_cap, m->spec_max ? 1 : 0};
+  *mu = v->host;
+  *var = v->host + v->cap;
+  *view = v;
   m->spec_out_dev = nullptr;
   m->spec_cap = 0;
   m->spec_valid = false;
@@ -1197,7 +1163,7 @@ int mfgp_release_view(void* view) {
       keep = true;
     }
   }
-  if (!keep) (void)hipHostFree(v->host);
+  if (!keep) v->owner().reset();
   delete v;
   return MFGP_OK;
 }
@@ -1348,6 +1314,16 @@ int mfgp_debug_read_f(mfgp_model* m, double* f_out, int64_t n_max, int64_t* rows
   for (int64_t i = 0; i < n; ++i)
     for (int64_t j = 0; j < n; ++j)
       f_out[i * n + j] = j <= i ? h[(size_t)(fblk_off(j / 64, ld) + (i - 64 * (j / 64)) * 64 + j % 64)] : 0.0;
+  return MFGP_OK;
+}
+// Tests only: what the library holds now, {device buffers, their bytes, pinned buffers, their
+// bytes}, the view pool's buffers and the views handed out included.
+int mfgp_debug_live(int64_t out[4]) {
+  if (!out) return set_err(MFGP_ERR_ARG, "null out");
+  out[0] = live_dev.count.load(std::memory_order_relaxed);
+  out[1] = live_dev.bytes.load(std::memory_order_relaxed);
+  out[2] = live_pin.count.load(std::memory_order_relaxed);
+  out[3] = live_pin.bytes.load(std::memory_order_relaxed);
   return MFGP_OK;
 }
 int64_t mfgp_model_nl(const mfgp_model* m) { return m ? m->NL : -1; }

@@ -20,11 +20,13 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/mfgp_hip.h"
 #include "mfgp_internal.h"
+#include "mfgp_own.h"
 
 namespace mfgp_host __attribute__((visibility("hidden"))) {
 
@@ -56,6 +58,70 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// ---- the device and pinned memory the library holds ----
+// Every buffer of a context, a model or a record is a Dev<T> (hipFree) or a Pin<T>
+// (hipHostFree); dev_alloc / pin_alloc are the only places that allocate, and the only
+// ones that report a refused allocation. live_dev / live_pin count what is held
+// (mfgp_debug_live), the view pool's buffers and handed-out views included.
+extern mfgp_own::Live live_dev, live_pin;   // (mfgp_capi.hip)
+inline void dev_free(void* p, size_t bytes) {
+  (void)hipFree(p);
+  live_dev.sub(bytes);
+}
+inline void pin_free(void* p, size_t bytes) {
+  (void)hipHostFree(p);
+  live_pin.sub(bytes);
+}
+template <class T>
+using Dev = mfgp_own::Owner<T, dev_free>;
+template <class T>
+using Pin = mfgp_own::Owner<T, pin_free>;
+// a refused allocation: HIP's last-error word cleared (the caller's next check of it, or
+// PyTorch's, sees none), MFGP_ERR_DEVICE with the bytes asked for
+inline int alloc_refused(const char* kind, size_t bytes) {
+  (void)hipGetLastError();
+  return set_err(MFGP_ERR_DEVICE, "out of %s memory: %zu bytes refused", kind, bytes);
+}
+enum : unsigned {
+  A_ZERO = 1,      // zeroed on the stream
+  A_2M = 2,        // whole 2 MiB units: small buffers that every GEMM workgroup of the lattice step
+                   // reads (the axis tables, the member lists) sit in one large page
+  A_NO_DRAIN = 4   // nothing enqueued reads o's old buffer (an empty or local owner)
+};
+// o's buffer replaced by a fresh one of `bytes` once the stream has drained (its launches
+// may read the old one), the old one freed first. On failure o is empty: the caller resets
+// the extent it keeps for o before the call, or commits it after.
+template <class T>
+int dev_alloc(Dev<T>& o, hipStream_t s, size_t bytes, unsigned flags = 0) {
+  if (!(flags & A_NO_DRAIN)) HIP_TRY(hipStreamSynchronize(s));
+  const size_t unit = size_t(2) << 20, want = (flags & A_2M) ? (bytes + unit - 1) / unit * unit : bytes;
+  if (const int rc = mfgp_own::fill(
+          o, want, live_dev, [](void** p, size_t b) { return (int)hipMalloc(p, b); },
+          [](size_t b) { return alloc_refused("device", b); }))
+    return rc;
+  if ((flags & A_ZERO) && bytes > 0 && hipMemsetAsync(o.get(), 0, bytes, s) != hipSuccess) {
+    o.reset();
+    return set_err(MFGP_ERR_DEVICE, "zero fill of %zu bytes failed", bytes);
+  }
+  return MFGP_OK;
+}
+// the pinned twin (hip_flags: hipHostMallocDefault / Mapped / Portable); the caller drains
+// the stream where launches may still write the old buffer
+template <class T>
+int pin_alloc(Pin<T>& o, size_t bytes, unsigned hip_flags) {
+  return mfgp_own::fill(
+      o, bytes, live_pin, [hip_flags](void** p, size_t b) { return (int)hipHostMalloc(p, b, hip_flags); },
+      [](size_t b) { return alloc_refused("pinned host", b); });
+}
+// the device address of a mapped pinned buffer
+template <class T>
+int pin_device(const Pin<T>& o, T*& dev) {
+  void* d = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&d, o.get(), 0));
+  dev = static_cast<T*>(d);
+  return MFGP_OK;
+}
 
 constexpr int RING = 64;       // descriptor upload slots
 constexpr int MAXB = 256;      // GPs per launch
@@ -106,18 +172,18 @@ enum PathCounter {
 }  // namespace mfgp_host
 
 struct mfgp_ctx {
+  __attribute__((visibility("hidden"))) ~mfgp_ctx() = default;   // (not a symbol of the library)
   int device = 0;
   hipStream_t own = nullptr;
   hipStream_t stream = nullptr;
   // descriptor ring
-  mfgp::GPDesc* h_ring = nullptr;  // pinned [RING][MAXB]
-  mfgp::GPDesc* d_ring = nullptr;  // device [RING][MAXB]
+  mfgp_host::Pin<mfgp::GPDesc> h_ring;  // pinned [RING][MAXB]
+  mfgp_host::Dev<mfgp::GPDesc> d_ring;  // device [RING][MAXB]
   hipEvent_t ring_ev[mfgp_host::RING];
   bool ring_used[mfgp_host::RING];
   int ring_pos = 0;
   // workspace (V scratch + device outputs for host-pointer calls)
-  double* ws = nullptr;
-  size_t ws_bytes = 0;
+  mfgp_host::Dev<double> ws;   // (its extent: ws.bytes())
   // timing: 0 off, 1 predict + factor launches, 2 predict launches only
   int timing = 0;
   int64_t timing_stride = 1, timing_seq = 0;   // bracket every stride-th eligible launch
@@ -129,14 +195,13 @@ struct mfgp_ctx {
   // failed factor is dropped from its model at mfgp_ctx_synchronize)
   struct AsyncStatus {
     mfgp_model* m;
-    int* dev;      // the model's status word (device)
-    int* host;     // its mapped host copy written by the launch (k_inc_stream1), or null: copy dev
+    int* dev;      // the model's status word (device; the model's, not owned here)
+    int* host;     // its mapped host copy written by the launch (k_inc_stream1; the model's), or null: copy dev
   };
   std::vector<AsyncStatus> async_status;
   // fp64 scratch in which the full predicts of MFGP_F32 models compute V
   // (k_predict re-reads its own rows), then rounded into their fp32 V
-  double* vscr = nullptr;
-  size_t vscr_bytes = 0;
+  mfgp_host::Dev<double> vscr;   // (its extent: vscr.bytes())
   int f32_group = 1;          // full predicts per k_predict launch that share vscr
   // incremental append / predict (bordered Cholesky + resident V); off = always
   // refactor and recompute V from scratch, as the reference does
@@ -179,16 +244,13 @@ struct mfgp_ctx {
                               // descriptors by value
                               // (MFGP_DESC_ARG=0: upload them, diagnostics)
   // pinned host staging of the status words
-  int* h_status = nullptr;
-  size_t h_status_n = 0;
+  mfgp_host::Pin<int> h_status;   // (bytes() / sizeof(int) words)
   // mfgp_nlml_batch: members per set of launches (0: as many as NLML_BATCH_SCRATCH
   // holds) and its scratch (NlmlLayout), grown on demand, kept for the next call and
   // given back by mfgp_ctx_trim
   int nlml_chunk = 0;
-  double* nb_dev = nullptr;
-  size_t nb_dev_bytes = 0;
-  double* nb_host = nullptr;   // pinned
-  size_t nb_host_bytes = 0;
+  mfgp_host::Dev<double> nb_dev;    // (their extents: bytes())
+  mfgp_host::Pin<double> nb_host;
 
   int ncu = 256;              // compute units (hipDeviceProp multiProcessorCount)
   // the path counters of the planners' loops (mfgp_sample_points,
@@ -200,10 +262,11 @@ struct mfgp_ctx {
 // The look-ahead record of a model (mfgp_query): the border of its last prospective
 // set, keyed by the model's serial and the set's rows and fidelities.
 struct mfgp_look_rec {
-  double* W = nullptr;       // [wld][64]: L^-1 K(X, X_P)
+  __attribute__((visibility("hidden"))) ~mfgp_look_rec() = default;   // (not a symbol of the library)
+  mfgp_host::Dev<double> W;      // [wld][64]: L^-1 K(X, X_P)
   int64_t wld = 0;
-  double* L22 = nullptr;     // [64][64] | L22inv [64][64] | ppts [64][2] (one allocation)
-  int* pfid = nullptr;       // [64] fidelities, then the border's status word
+  mfgp_host::Dev<double> L22;    // [64][64] | L22inv [64][64] | ppts [64][2] (one allocation)
+  mfgp_host::Dev<int> pfid;      // [64] fidelities, then the border's status word
   bool valid = false;        // the border below is stored for (serial, P, key)
   uint64_t serial = 0;
   int P = 0;
@@ -214,14 +277,15 @@ struct mfgp_look_rec {
 // the lattice axes' Gram matrices per field, keyed by the model's serial, and the
 // lattice indices of its training rows.
 struct mfgp_sample_rec {
+  __attribute__((visibility("hidden"))) ~mfgp_sample_rec() = default;   // (not a symbol of the library)
   bool valid = false;        // the axis factors below belong to `serial`
   uint64_t serial = 0;
   int fields = 0, nx = 0, ny = 0;
   int rx[2] = {0, 0}, ry[2] = {0, 0};
-  double* fac = nullptr;     // device: per field Ax [nx][rx] | AyT [ry][ny]
+  mfgp_host::Dev<double> fac;   // device: per field Ax [nx][rx] | AyT [ry][ny]
   size_t fac_n = 0;          // doubles allocated
   size_t off_ax[2] = {0, 0}, off_ay[2] = {0, 0};
-  int* lidx = nullptr;       // device [lidx_cap]: px | (py << 16) per training row
+  mfgp_host::Dev<int> lidx;     // device [lidx_cap]: px | (py << 16) per training row
   int64_t lidx_cap = 0;
   bool lidx_valid = false;   // lidx holds the N rows of `lidx_serial`
   uint64_t lidx_serial = 0;
@@ -229,9 +293,15 @@ struct mfgp_sample_rec {
 };
 
 struct mfgp_model {
-  __attribute__((visibility("hidden"))) ~mfgp_model() = default;   // (in two files now: not a symbol of the library)
+  // (not a symbol of the library) every buffer below frees itself; the two records are the model's
+  __attribute__((visibility("hidden"))) ~mfgp_model() {
+    delete look;
+    delete samp;
+  }
   mfgp_ctx* ctx = nullptr;
-  int* gate_dev = nullptr;  // device gate of every step of this model (the planners' loops: 0 = skip)
+  // device gate of every step of this model (the planners' loops: 0 = skip); points into
+  // the running planner's state, not owned
+  int* gate_dev = nullptr;
   int kind = MFGP_SF;
   int dtype = MFGP_F64;     // precision of the resident V (MFGP_F32: fp32 storage and stream)
   int nhyp = 4;
@@ -239,18 +309,18 @@ struct mfgp_model {
   double jitter = 1e-8;
   // training set (device)
   int64_t NL = 0, NH = 0, cap = 0;
-  double* X = nullptr;  // [cap,2]
-  double* y = nullptr;  // [cap]
+  mfgp_host::Dev<double> X;  // [cap,2]
+  mfgp_host::Dev<double> y;  // [cap]
   // factor (device)
   int64_t ld = 0;
-  double* A = nullptr;     // [ld,ld]
-  double* Linv = nullptr;  // [ld/NB][TILE]
-  double* zv = nullptr;     // [cap] z = L^-1 (y - m)
-  double* iscr = nullptr;   // incremental-append scratch (inc_scratch_doubles(cap))
-  int* status = nullptr;
-  int* status_host = nullptr;       // mapped pinned words the single-GP fused launch publishes into:
+  mfgp_host::Dev<double> A;     // [ld,ld]
+  mfgp_host::Dev<double> Linv;  // [ld/NB][TILE]
+  mfgp_host::Dev<double> zv;     // [cap] z = L^-1 (y - m)
+  mfgp_host::Dev<double> iscr;   // incremental-append scratch (inc_scratch_doubles(cap))
+  mfgp_host::Dev<int> status;
+  mfgp_host::Pin<int> status_host;       // mapped pinned words the single-GP fused launch publishes into:
                                     // [0] its status (last act), [1] the L22 verdict (pd_host)
-  int* status_host_dev = nullptr;   // its device address
+  int* status_host_dev = nullptr;   // its device address (an alias of status_host, not owned)
   bool factored = false;
   int64_t factor_N = -1;    // rows [0, factor_N) of A / Linv / zv hold the current factor
   int64_t ablk = 0;         // 64-row blocks of A / Linv initialised (assembled or padded)
@@ -258,16 +328,16 @@ struct mfgp_model {
   double factor_jitter = 0.0;
   // grid (device)
   int64_t M = 0, Mcap = 0;
-  double* grid = nullptr;
+  mfgp_host::Dev<double> grid;
   mfgp::GridLattice lat{};        // lattice structure of the grid (nx == 0: none)
   std::vector<double> hax, hay;   // the lattice's axis values (host copy, for rows_on_cells)
   // resident V = L^-1 psi^T [vtiles][vld][PBM] (double, or float for MFGP_F32);
   // rows [0, v_n) valid for the current factor and grid
-  void* V = nullptr;
+  mfgp_host::Dev<void> V;
   int64_t vld = 0, vtiles = 0, v_n = 0;
-  double* tred = nullptr;     // [vtiles][2] per-tile (max, argmax) of var, then the tiles' arrival counter
+  mfgp_host::Dev<double> tred;     // [vtiles][2] per-tile (max, argmax) of var, then the tiles' arrival counter
   int64_t tred_n = 0;         // doubles of tred
-  unsigned* sync = nullptr;   // k_inc_stream hand-off words {arrivals, L21 ready, L22 ready} (zeroed)
+  mfgp_host::Dev<unsigned> sync;   // k_inc_stream hand-off words {arrivals, L21 ready, L22 ready} (zeroed)
   unsigned epoch = 0;         // last k_inc_stream epoch of this model
   // the compact bordered rows in iscr (inc_l21c_offset) hold rows [l21c_n0, l21c_N)
   // bordered onto l21c_n0 factor rows (-1: none)
@@ -276,8 +346,8 @@ struct mfgp_model {
   // predict runs the bordered append and the one-pass predict as one launch and
   // keeps mu | var in `spec_out` (mapped pinned, [2][M]) for the predict that
   // follows; any change to the model drops them
-  double* spec_out = nullptr;
-  double* spec_out_dev = nullptr;
+  mfgp_host::Pin<double> spec_out;
+  double* spec_out_dev = nullptr;   // its device address (an alias of spec_out, not owned)
   int64_t spec_cap = 0;
   bool spec_valid = false;
   // spec_out's trailer [2 cap] = (max var, its first argmax) holds the fused var
@@ -289,8 +359,7 @@ struct mfgp_model {
   int64_t cnt[mfgp_host::N_COUNTERS] = {0};
   mfgp_look_rec* look = nullptr;   // look-ahead record (allocated by the first mfgp_query, not cloned)
   mfgp_sample_rec* samp = nullptr;   // sample record (allocated by the first mfgp_sample_*, not cloned)
-  unsigned* csr = nullptr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
-  int64_t csr_n = 0;           // (bytes)
+  mfgp_host::Dev<unsigned> csr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
   // state generation: a new factor from scratch, a new grid or new hyperparameters
   // start a new one (the resident posterior, F and the tables belong to one)
   uint64_t gen = 1;
@@ -301,43 +370,43 @@ struct mfgp_model {
   uint64_t serial = 0;
   // resident posterior: two buffers [mu | var] of M each, written by every predict
   // (incremental mode); buffer b holds the posterior of the res_n[b] leading rows
-  double* res = nullptr;
+  mfgp_host::Dev<double> res;
   int64_t res_M = 0;
   int64_t res_n[2] = {-1, -1};
   uint64_t res_gen[2] = {0, 0};
   int res_depth[2] = {0, 0};   // lattice steps since var / mu were computed from V
   uint64_t res_tick[2] = {0, 0}, tick = 0;
   // lattice-separable step state (allocated on first use)
-  double* F = nullptr;        // explicit L^-1 [F_ld][F_ld], rows [0, F_n) current for generation F_gen
-  float* Ff = nullptr;        // MFGP_F32: F in fp32 (the rows the lattice steps stream and extend)
+  mfgp_host::Dev<double> F;        // explicit L^-1 [F_ld][F_ld], rows [0, F_n) current for generation F_gen
+  mfgp_host::Dev<float> Ff;        // MFGP_F32: F in fp32 (the rows the lattice steps stream and extend)
   int64_t F_ld = 0, F_n = 0;
   uint64_t F_gen = 0;
-  double* tab = nullptr;      // separable tables [4][tab_ld][tabw], rows [0, tab_n)
+  mfgp_host::Dev<double> tab;      // separable tables [4][tab_ld][tabw], rows [0, tab_n)
   int64_t tab_ld = 0, tabw = 0, tab_n = 0;
   uint64_t tab_gen = 0;
-  double* wv = nullptr;       // w [wv_ld][KINC]
+  mfgp_host::Dev<double> wv;       // w [wv_ld][KINC]
   int64_t wv_ld = 0;
-  unsigned* wflag = nullptr;  // [wv_ld / 64 + 2]
-  unsigned* wcnt = nullptr;   // [wv_ld / 64 + 2]
-  double* wpart = nullptr;    // [LAT_WU_MAX + wv_ld / 64 + 1][1024]
-  double* gpart = nullptr;    // split-K partials
+  mfgp_host::Dev<unsigned> wflag;  // [wv_ld / 64 + 2]
+  mfgp_host::Dev<unsigned> wcnt;   // [wv_ld / 64 + 2]
+  mfgp_host::Dev<double> wpart;    // [LAT_WU_MAX + wv_ld / 64 + 1][1024]
+  mfgp_host::Dev<double> gpart;    // split-K partials
   size_t gpart_n = 0;
-  unsigned* gcnt = nullptr;   // per GEMM tile
+  mfgp_host::Dev<unsigned> gcnt;   // per GEMM tile
   int64_t gcnt_n = 0;
-  int* lidx = nullptr;        // lattice indices per training row [tab_ld], rows [0, tab_n) (with the tables)
-  double* axt = nullptr;      // axis tables [4][tabw + 1][tabw], current for generation axt_gen
+  mfgp_host::Dev<int> lidx;   // lattice indices per training row [tab_ld], rows [0, tab_n) (with the tables)
+  mfgp_host::Dev<double> axt;      // axis tables [4][tabw + 1][tabw], current for generation axt_gen
   int64_t axt_w = 0;
   uint64_t axt_gen = 0;
-  double* zb = nullptr;       // Z rows [P][zrows][tabw][zb_ka]
+  mfgp_host::Dev<double> zb;       // Z rows [P][zrows][tabw][zb_ka]
   int64_t zb_rows = 0, zb_w = 0;
   int zb_ka = 0;
-  unsigned* zflag = nullptr;  // [zflag_n]
+  mfgp_host::Dev<unsigned> zflag;  // [zflag_n]
   int64_t zflag_n = 0;
-  unsigned* ldone = nullptr;  // [4] lattice phase hand-offs (arrivals | flag, twice)
-  int* zvl = nullptr;         // [2][zb_rows + 1]
+  mfgp_host::Dev<unsigned> ldone;  // [4] lattice phase hand-offs (arrivals | flag, twice)
+  mfgp_host::Dev<int> zvl;         // [2][zb_rows + 1]
   // the column store of V, Vc[cell][vc_ld] in V's element type: rows [0, vc_n) equal V's for
   // generation vc_gen (allocated with the lattice state where the budget allows: ensure_vcol)
-  void* Vc = nullptr;
+  mfgp_host::Dev<void> Vc;
   int64_t vc_ld = 0, vc_M = 0, vc_n = 0;
   uint64_t vc_gen = 0;
   int64_t vc_deny_ld = -1, vc_deny_M = -1, vc_deny_budget = -2;   // the shape and budget last refused
@@ -346,6 +415,13 @@ struct mfgp_model {
 namespace mfgp_host __attribute__((visibility("hidden"))) {
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// A model destroyed with the scope unless release()d: one under construction
+// (mfgp_model_create, mfgp_clone), a scratch model (mfgp_nlml).
+struct ModelDestroy {
+  void operator()(mfgp_model* m) const { mfgp_model_destroy(m); }
+};
+using ModelGuard = std::unique_ptr<mfgp_model, ModelDestroy>;
 
 // An eager append that returned at its L22 verdict (mfgp_ctx::early_pd) may still
 // run: every entry point waits for it, and takes its status, before it reads or
@@ -364,26 +440,6 @@ struct Entry {
     if (rc == MFGP_OK) rc = check_model(m);
   }
 };
-
-// Small buffers that every GEMM workgroup of the lattice step reads (the axis
-// tables, the member lists): whole 2 MiB units, so that they sit in one large page
-inline hipError_t hip_malloc_2m(void** p, size_t bytes) {
-  const size_t unit = size_t(2) << 20;
-  return hipMalloc(p, (bytes + unit - 1) / unit * unit);
-}
-
-// A device buffer replaced by a fresh one of `bytes` once the stream has drained (its
-// launches may read the old one); zeroed on the stream when `zero`, in whole 2 MiB
-// units when `big_page`. p is null if the allocation fails.
-template <class T>
-int renew(hipStream_t s, T*& p, size_t bytes, bool zero, bool big_page = false) {
-  HIP_TRY(hipStreamSynchronize(s));
-  if (p) HIP_TRY(hipFree(p));
-  p = nullptr;
-  HIP_TRY(big_page ? hip_malloc_2m(reinterpret_cast<void**>(&p), bytes) : hipMalloc(&p, bytes));
-  if (zero) HIP_TRY(hipMemsetAsync(p, 0, bytes, s));
-  return MFGP_OK;
-}
 
 // Offsets of the pieces of a workspace, in the order they are taken, each rounded up
 // to 256 bytes; `end` is the room they need.
@@ -508,9 +564,6 @@ struct CovWork {
 size_t cov_work_bytes(const mfgp_model* m, int64_t rows);
 int cov_work_init(mfgp_model* m, char* base, int64_t rows, CovWork& w);
 int cov_work_run(mfgp_model* m, CovWork& w, int64_t n_rows);
-
-// mfgp_train.hip
-int free_nlml_scratch(mfgp_ctx* c);
 
 }  // namespace mfgp_host
 

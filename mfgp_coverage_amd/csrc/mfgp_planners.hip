@@ -151,8 +151,8 @@ struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no sym
   int count;
   std::vector<PlanSave> sv;
   int entered = 0;            // the models plan_enter has saved
-  char* ws = nullptr;         // the scratch: the run's own (`own`) or the context's workspace
-  bool owned = false;
+  char* ws = nullptr;         // the scratch: the run's own (`mine`, freed with the run) or the context's workspace
+  Dev<char> mine;
   int64_t* state = nullptr;   // device [count][2]: {gate, rows appended}
   std::vector<int64_t> st;    // its host image: {1, 0} each for `open`, then as of the last chunk_end
   std::vector<int> live;      // the models whose status chunk_end reads (the batched loop prunes it)
@@ -170,9 +170,8 @@ struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no sym
     return reinterpret_cast<T*>(ws + o);
   }
   bool own(size_t bytes) {
-    owned = hipMalloc(&ws, bytes) == hipSuccess;
-    if (!owned) (void)hipGetLastError();
-    return owned;
+    ws = dev_alloc(mine, c->stream, bytes, A_NO_DRAIN) == MFGP_OK ? mine.get() : nullptr;
+    return ws != nullptr;
   }
   // plan_enter for each model; `room`: the models' plan_res_doubles, one after another
   int enter(double* room) {
@@ -184,7 +183,7 @@ struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no sym
   int fail(int code) {
     for (int b = 0; b < entered; ++b) (void)plan_leave(t[b], sv[b], true);
     (void)hipStreamSynchronize(c->stream);   // (the restore copies read ws)
-    if (owned) (void)hipFree(ws);
+    mine.reset();
     return code;
   }
   // the gates opened, the counts zeroed
@@ -225,7 +224,7 @@ struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no sym
     entered = 0;
     const int sync = ctx_sync ? mfgp_ctx_synchronize(c)
                               : (hipStreamSynchronize(c->stream) == hipSuccess ? MFGP_OK : MFGP_ERR_DEVICE);
-    if (owned) (void)hipFree(ws);
+    mine.reset();
     return rc ? rc : sync;
   }
 };
@@ -262,7 +261,7 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
   const size_t o_res = lay.take(sizeof(double) * plan_res_doubles(t));
   if ((rc = ensure_ws(c, lay.end))) return rc;
   PlanRun run("sample_points", c, &t, 1);
-  run.ws = reinterpret_cast<char*>(c->ws);
+  run.ws = reinterpret_cast<char*>(c->ws.get());
   double *mu_s = run.at(o_mu), *var_s = run.at(o_var), *vmax = run.at(o_misc), *pts = run.at(o_pts);
   int64_t* vargmax = reinterpret_cast<int64_t*>(vmax + 1);
   run.state = vargmax + 1;
@@ -592,7 +591,7 @@ int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t
       if ((rc = batch_run(&t, 1, xn, yn, &one, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, true, true))) return run.fail(rc);
       if (done + it + 1 >= n_points) break;   // the last pick: no score is read after it
       const int64_t row = t->NL + t->NH - 1;
-      if (launch_plan_x(static_cast<const double*>(t->V), t->vld, row, M, dw, g, x, tau, gate, s) != hipSuccess)
+      if (launch_plan_x(static_cast<const double*>(t->V.get()), t->vld, row, M, dw, g, x, tau, gate, s) != hipSuccess)
         return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
       if ((rc = cov_work_run(t, cw, row + 1))) return run.fail(rc);
     }

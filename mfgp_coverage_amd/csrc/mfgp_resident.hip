@@ -120,7 +120,7 @@ int cov_work_init(mfgp_model* m, char* base, int64_t rows, CovWork& w) {
 int cov_work_run(mfgp_model* m, CovWork& w, int64_t n_rows) {
   if (n_rows > w.a.pld) return set_err(MFGP_ERR_DEVICE, "covariance product: %lld rows exceed the scratch's %lld",
                                        (long long)n_rows, (long long)w.a.pld);
-  w.a.V = static_cast<const double*>(m->V);
+  w.a.V = static_cast<const double*>(m->V.get());
   w.a.vld = m->vld;
   w.a.N = n_rows;
   w.a.kx = nullptr;
@@ -163,7 +163,7 @@ int mfgp_cov_block(mfgp_model* m, const int64_t* rows, int64_t na, const int64_t
   const size_t o_idx = lay.take(sizeof(int64_t) * (size_t)((rows ? na : 0) + (cols ? nb : 0)));
   const size_t o_out = lay.take(host ? sizeof(double) * (size_t)na * nb : 0);
   if ((rc = ensure_ws(c, lay.end))) return rc;
-  char* ws = reinterpret_cast<char*>(c->ws);
+  char* ws = reinterpret_cast<char*>(c->ws.get());
   int64_t* drows = rows ? reinterpret_cast<int64_t*>(ws + o_idx) : nullptr;
   int64_t* dcols = cols ? reinterpret_cast<int64_t*>(ws + o_idx) + (rows ? na : 0) : nullptr;
   if (rows) HIP_TRY(hipMemcpyAsync(drows, rows, sizeof(int64_t) * na, hipMemcpyHostToDevice, c->stream));
@@ -227,7 +227,7 @@ int mfgp_var_reduction(mfgp_model* m, const int64_t* cand, int64_t nc, const dou
   const size_t o_best = lay.take(sizeof(double) * MFGP_IVR_MAXW);
   const size_t o_bp = lay.take(sizeof(int64_t) * MFGP_IVR_MAXW);
   if ((rc = ensure_ws(c, lay.end))) return rc;
-  char* ws = reinterpret_cast<char*>(c->ws);
+  char* ws = reinterpret_cast<char*>(c->ws.get());
   int64_t* dcand = cand ? reinterpret_cast<int64_t*>(ws + o_cand) : nullptr;
   if (cand) HIP_TRY(hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, c->stream));
   const StagedIn sw(w, nw, M, ldw, w_host, ws + o_w);
@@ -277,7 +277,7 @@ int mfgp_cov_apply(mfgp_model* m, const double* x, int nx, int64_t ldx, double* 
   const size_t o_out = lay.take(o_host ? sizeof(double) * (size_t)nx * M : 0);
   const size_t o_work = lay.take(cov_work_bytes(m, N));
   if ((rc = ensure_ws(c, lay.end))) return rc;
-  char* ws = reinterpret_cast<char*>(c->ws);
+  char* ws = reinterpret_cast<char*>(c->ws.get());
   const StagedIn sx(x, nx, M, ldx, x_host, ws + o_x);
   HIP_TRY(sx.upload(c->stream));
   const StagedOut so(out, ldo, o_host, ws + o_out, M);
@@ -346,14 +346,14 @@ int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq, const double* XL_new
     if (!m->look) m->look = new mfgp_look_rec();
     mfgp_look_rec* k = m->look;
     const int64_t wld = std::max<int64_t>(prow_blocks(N) * PRB, PRB);
-    if (!k->L22) {
-      HIP_TRY(hipMalloc(&k->L22, sizeof(double) * (2 * TILE + 2 * LOOK_MAX)));
-      HIP_TRY(hipMalloc(&k->pfid, sizeof(int) * (LOOK_MAX + 1)));
+    if (!k->L22 || !k->pfid) {   // (the pair: a record with one of them allocates again)
+      if ((rc = dev_alloc(k->L22, c->stream, sizeof(double) * (2 * TILE + 2 * LOOK_MAX), A_NO_DRAIN))) return rc;
+      if ((rc = dev_alloc(k->pfid, c->stream, sizeof(int) * (LOOK_MAX + 1), A_NO_DRAIN))) return rc;
     }
     if (k->wld < wld) {
       k->wld = 0;
       k->valid = false;
-      if ((rc = renew(c->stream, k->W, sizeof(double) * wld * PBM, false))) return rc;
+      if ((rc = dev_alloc(k->W, c->stream, sizeof(double) * wld * PBM))) return rc;
       k->wld = wld;
     }
     std::vector<double> key(hp);
@@ -400,7 +400,7 @@ int mfgp_query(mfgp_model* m, const double* Xq, int64_t nq, const double* XL_new
   const size_t o_cov = lay.take(cov_host ? sizeof(double) * (size_t)nq * nq : 0);
   const size_t o_scr = lay.take(sizeof(double) * (size_t)ntiles_grid(chunk) * vld * PBM);
   if ((rc = ensure_ws(c, lay.end))) return rc;
-  char* ws = reinterpret_cast<char*>(c->ws);
+  char* ws = reinterpret_cast<char*>(c->ws.get());
   double* outs[3] = {mu, var0, var};
   a.scr = reinterpret_cast<double*>(ws + o_scr);
   a.vld = vld;
@@ -551,10 +551,8 @@ static int sample_record(mfgp_model* m, const char* who) {
   }
   if (fields == 1) k->rx[1] = k->ry[1] = 0;
   if (host.size() > k->fac_n) {
-    if (k->fac) HIP_TRY(hipFree(k->fac));
-    k->fac = nullptr;
     k->fac_n = 0;
-    HIP_TRY(hipMalloc(&k->fac, sizeof(double) * host.size()));
+    if (const int rc = dev_alloc(k->fac, c->stream, sizeof(double) * host.size(), A_NO_DRAIN)) return rc;
     k->fac_n = host.size();
   }
   HIP_TRY(hipMemcpy(k->fac, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
@@ -606,10 +604,8 @@ static int sample_lidx(mfgp_model* m, const char* who) {
       if (li[i] < 0 && k->off_row < 0) k->off_row = i;
     }
     if (k->lidx_cap < N) {
-      if (k->lidx) HIP_TRY(hipFree(k->lidx));
-      k->lidx = nullptr;
       k->lidx_cap = 0;
-      HIP_TRY(hipMalloc(&k->lidx, sizeof(int) * round_up(N, 1024)));
+      if (const int rc = dev_alloc(k->lidx, c->stream, sizeof(int) * round_up(N, 1024), A_NO_DRAIN)) return rc;
       k->lidx_cap = round_up(N, 1024);
     }
     HIP_TRY(hipMemcpy(k->lidx, li.data(), sizeof(int) * N, hipMemcpyHostToDevice));
@@ -680,7 +676,7 @@ int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64
   const size_t o_z = lay.take(z_dev ? 0 : sizeof(double) * (size_t)SAMPLE_CHUNK * std::max<int64_t>(nz, 1));
   const size_t o_o = lay.take(o_dev ? 0 : sizeof(double) * (size_t)SAMPLE_CHUNK * M);
   if ((rc = ensure_ws(c, lay.end))) return rc;
-  char* ws = reinterpret_cast<char*>(c->ws);
+  char* ws = reinterpret_cast<char*>(c->ws.get());
   const Hyp h = derive_hyp(m->kind, m->hyp, m->jitter);
   const GridLattice& L = m->lat;
   SampleArgs a{};
@@ -719,7 +715,7 @@ int mfgp_sample_posterior(mfgp_model* m, const double* normals, int64_t S, int64
   a.A = m->A;
   a.Linv = m->Linv;
   a.ld = m->ld;
-  a.V = reinterpret_cast<const double*>(m->V);
+  a.V = static_cast<const double*>(m->V.get());
   a.vld = m->vld;
   for (int64_t s0 = 0; s0 < S; s0 += SAMPLE_CHUNK) {
     const int64_t sc = std::min<int64_t>(SAMPLE_CHUNK, S - s0);

@@ -212,18 +212,15 @@ int assign_predict_scratch(mfgp_ctx* c, GPDesc* hd, int count) {
   per = WsLayout::up(per);
   if (per == 0) return MFGP_OK;
   int g = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, F32_SCRATCH / per));
-  if (per * g > c->vscr_bytes) {
+  if (per * g > c->vscr.bytes()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->vscr) HIP_TRY(hipFree(c->vscr));
-    c->vscr = nullptr;
-    c->vscr_bytes = 0;
+    c->vscr.reset();
     // at most half of the free HBM (the resident state of the models comes first);
     // mfgp_ctx_trim gives the scratch back
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess && per * g > fr / 2)
       g = (int)std::max<size_t>(1, std::min<size_t>((size_t)g, fr / 2 / per));
-    HIP_TRY(hipMalloc(&c->vscr, per * g));
-    c->vscr_bytes = per * g;
+    if (const int rc = dev_alloc(c->vscr, c->stream, per * g, A_NO_DRAIN)) return rc;
   }
   c->f32_group = g;
   for (int i = 0; i < count; ++i) hd[i].V = c->vscr + (per / sizeof(double)) * (i % g);
@@ -263,9 +260,7 @@ constexpr int64_t TRINV_WS_MAX = int64_t(2) << 30;
 
 static int ensure_sync(mfgp_model* m) {
   if (m->sync) return MFGP_OK;
-  HIP_TRY(hipMalloc(&m->sync, 4 * sizeof(unsigned)));
-  HIP_TRY(hipMemsetAsync(m->sync, 0, 4 * sizeof(unsigned), m->ctx->stream));
-  return MFGP_OK;
+  return dev_alloc(m->sync, m->ctx->stream, 4 * sizeof(unsigned), A_ZERO | A_NO_DRAIN);
 }
 
 // Bordered appends and their one-pass predicts in one k_inc_stream launch (dd == null:
@@ -318,7 +313,7 @@ static int enqueue_inc_lat(mfgp_ctx* c, const GPDesc* dd, const GPDesc* hd, int 
       size_t free_b = 0, total_b = 0;
       int64_t budget = TRINV_WS_MAX;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        budget = std::min<int64_t>(budget, (int64_t)((free_b + c->ws_bytes) / 2));
+        budget = std::min<int64_t>(budget, (int64_t)((free_b + c->ws.bytes()) / 2));
       const int64_t per_gp = (int64_t)sizeof(double) * tstride;
       chunk = (int)std::max<int64_t>(1, std::min<int64_t>(count, budget / std::max<int64_t>(per_gp, 1)));
       int rc = ensure_ws(c, sizeof(double) * (size_t)(tstride * chunk));
@@ -694,13 +689,16 @@ int BatchCall::fill_factor_descs(int b0, int nb, GPDesc* hd, int& ninc, int& nfu
 // the model's deferred status entry told to read the word.
 static int publish_mapped_status(mfgp_ctx* c, mfgp_model* m, GPDesc& d) {
   if (!m->status_host) {
-    HIP_TRY(hipHostMalloc(&m->status_host, 2 * sizeof(int), hipHostMallocMapped));
-    void* dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dev, m->status_host, 0));
-    m->status_host_dev = static_cast<int*>(dev);
+    int rc;
+    if ((rc = pin_alloc(m->status_host, 2 * sizeof(int), hipHostMallocMapped))) return rc;
+    if ((rc = pin_device(m->status_host, m->status_host_dev))) {
+      m->status_host.reset();
+      return rc;
+    }
   }
-  *reinterpret_cast<volatile int*>(m->status_host) = STATUS_UNSET;
-  reinterpret_cast<volatile int*>(m->status_host)[1] = STATUS_UNSET;
+  volatile int* const words = m->status_host.get();
+  words[0] = STATUS_UNSET;
+  words[1] = STATUS_UNSET;
   d.status_host = m->status_host_dev;
   d.pd_host = m->status_host_dev + 1;
   for (auto it = c->async_status.rbegin(); it != c->async_status.rend(); ++it)
@@ -952,7 +950,7 @@ int spec_append_predict(mfgp_model* m, const double* X, const double* y, int64_t
   int rc = settle(c);
   if (rc == MFGP_OK) rc = ensure_spec_out(m);
   if (rc) return rc;
-  if (m->status_host) reinterpret_cast<volatile int*>(m->status_host)[1] = STATUS_UNSET;
+  if (m->status_host) static_cast<volatile int*>(m->status_host.get())[1] = STATUS_UNSET;
   // (the fused var max / argmax into the buffer's trailer: the launch's last cell
   // group reduces the groups' partials for the status word anyway)
   double* tr = m->spec_out_dev + 2 * m->spec_cap;
@@ -966,7 +964,7 @@ int spec_append_predict(mfgp_model* m, const double* X, const double* y, int64_t
     // factor can fail with) into the model's second mapped word: a positive
     // definite step returns now, and the next entry point settles the launch
     // (its outputs, hang guards) before anything reads or reuses its buffers
-    const volatile int* w = reinterpret_cast<const volatile int*>(m->status_host) + 1;
+    const volatile int* w = static_cast<const volatile int*>(m->status_host.get()) + 1;
     const auto t0 = std::chrono::steady_clock::now();
     while (*w == STATUS_UNSET) {
       __builtin_ia32_pause();

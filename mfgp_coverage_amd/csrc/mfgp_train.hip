@@ -84,32 +84,15 @@ NlmlLayout nlml_layout(int64_t ld, int64_t np, int64_t C, bool grad) {
 }
 int ensure_nlml_scratch(mfgp_ctx* c, const NlmlLayout& l) {
   const size_t dev = sizeof(double) * (size_t)l.total, host = sizeof(double) * (size_t)l.h_total;
-  if (dev > c->nb_dev_bytes) {
-    c->nb_dev_bytes = 0;
-    if (const int rc = renew(c->stream, c->nb_dev, dev, false)) return rc;
-    c->nb_dev_bytes = dev;
-  }
-  if (host > c->nb_host_bytes) {
+  int rc;
+  if (dev > c->nb_dev.bytes() && (rc = dev_alloc(c->nb_dev, c->stream, dev))) return rc;
+  if (host > c->nb_host.bytes()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->nb_host) HIP_TRY(hipHostFree(c->nb_host));
-    c->nb_host = nullptr;
-    c->nb_host_bytes = 0;
-    HIP_TRY(hipHostMalloc(&c->nb_host, host, hipHostMallocDefault));
-    c->nb_host_bytes = host;
+    if ((rc = pin_alloc(c->nb_host, host, hipHostMallocDefault))) return rc;
   }
   return MFGP_OK;
 }
 }  // namespace
-
-int mfgp_host::free_nlml_scratch(mfgp_ctx* c) {
-  if (c->nb_dev) HIP_TRY(hipFree(c->nb_dev));
-  c->nb_dev = nullptr;
-  c->nb_dev_bytes = 0;
-  if (c->nb_host) HIP_TRY(hipHostFree(c->nb_host));
-  c->nb_host = nullptr;
-  c->nb_host_bytes = 0;
-  return MFGP_OK;
-}
 
 extern "C" {
 
@@ -130,41 +113,36 @@ int mfgp_nlml(mfgp_model* m, const double* hyp, int nhyp, double* nlml, double* 
       for (int p = 0; p < nhyp; ++p) grad[p] = 0.0;
     return MFGP_OK;
   }
-  mfgp_model* t = nullptr;   // scratch factor of K(hyp)
+  // scratch factor of K(hyp) and the kernels' scratch: all of it goes on every return
+  mfgp_model* t = nullptr;
   if ((rc = mfgp_model_create(c, m->kind, MFGP_F64, hyp, nhyp, m->jitter, &t))) return rc;
-  double *Xi = nullptr, *Kv = nullptr, *al = nullptr, *part = nullptr, *val = nullptr;
-  auto done = [&](int code) {
-    if (Xi) (void)hipFree(Xi);
-    if (Kv) (void)hipFree(Kv);
-    if (al) (void)hipFree(al);
-    if (part) (void)hipFree(part);
-    if (val) (void)hipFree(val);
-    mfgp_model_destroy(t);
-    return code;
-  };
-  if ((rc = ensure_cap(t, N))) return done(rc);
+  const ModelGuard scratch(t);
+  Dev<double> Xi, Kv, al, part, val;
+  if ((rc = ensure_cap(t, N))) return rc;
   HIP_TRY(hipMemcpyAsync(t->X, m->X, sizeof(double) * 2 * N, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(t->y, m->y, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
   t->NL = m->NL;
   t->NH = m->NH;
-  if ((rc = factor_one(t))) return done(rc);   // LinAlgError as the reference's cholesky (gp:101 / 380)
+  if ((rc = factor_one(t))) return rc;   // LinAlgError as the reference's cholesky (gp:101 / 380)
   int slot;
   GPDesc* hd = acquire_slot(c, slot, rc);
-  if (!hd) return done(rc);
+  if (!hd) return rc;
   fill_desc(hd[0], t);
   const GPDesc* dd = nullptr;
-  if ((rc = upload_slot(c, slot, 1, &dd))) return done(rc);
-  if (hipMalloc(&val, sizeof(double) * 2) != hipSuccess) return done(set_err(MFGP_ERR_DEVICE, "alloc"));
-  if (launch_nlml_value(dd, 1, val, c->stream) != hipSuccess) return done(set_err(MFGP_ERR_DEVICE, "launch"));
+  if ((rc = upload_slot(c, slot, 1, &dd))) return rc;
+  if ((rc = dev_alloc(val, c->stream, sizeof(double) * 2, A_NO_DRAIN))) return rc;
+  if (launch_nlml_value(dd, 1, val, c->stream) != hipSuccess) return set_err(MFGP_ERR_DEVICE, "launch");
   const int64_t ld = t->ld, np = nlml_partials(N);
   if (grad) {
-    if (hipMalloc(&Xi, sizeof(double) * ld * ld) != hipSuccess || hipMalloc(&Kv, sizeof(double) * ld * ld) != hipSuccess ||
-        hipMalloc(&al, sizeof(double) * ld) != hipSuccess || hipMalloc(&part, sizeof(double) * np) != hipSuccess)
-      return done(set_err(MFGP_ERR_DEVICE, "nlml: out of device memory"));
+    if ((rc = dev_alloc(Xi, c->stream, sizeof(double) * ld * ld, A_NO_DRAIN)) ||
+        (rc = dev_alloc(Kv, c->stream, sizeof(double) * ld * ld, A_NO_DRAIN)) ||
+        (rc = dev_alloc(al, c->stream, sizeof(double) * ld, A_NO_DRAIN)) ||
+        (rc = dev_alloc(part, c->stream, sizeof(double) * np, A_NO_DRAIN)))
+      return rc;
     if (launch_nlml_grad(dd, N, Xi, Kv, al, part, c->stream) != hipSuccess)
-      return done(set_err(MFGP_ERR_DEVICE, "nlml: launch failed"));
+      return set_err(MFGP_ERR_DEVICE, "nlml: launch failed");
   }
-  if ((rc = release_slot(c, slot))) return done(rc);
+  if ((rc = release_slot(c, slot))) return rc;
   double v[2] = {0.0, 0.0};
   std::vector<double> hp, ha;
   HIP_TRY(hipMemcpyAsync(v, val, sizeof(v), hipMemcpyDeviceToHost, c->stream));
@@ -176,7 +154,7 @@ int mfgp_nlml(mfgp_model* m, const double* hyp, int nhyp, double* nlml, double* 
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   nlml_finish(m, hyp, N, v, hp.data(), np, ha.data(), nlml, grad);
-  return done(MFGP_OK);
+  return MFGP_OK;
 }
 
 // mfgp_nlml for S hyperparameter vectors in chunks of C members: per chunk one
@@ -223,24 +201,24 @@ int mfgp_nlml_batch(mfgp_model* m, const double* hyps, int S, int nhyp, double* 
     GPDesc* hd = acquire_slot(c, slot, rc);
     if (!hd) return rc;
     for (int i = 0; i < cnt; ++i) {
-      mfgp_model t;   // a scratch factor of K(hyps[s0 + i]) over the caller's rows (a descriptor's worth of it)
-      t.ctx = c;
-      t.kind = m->kind;
-      t.dtype = MFGP_F64;
-      t.nhyp = nhyp;
-      std::memcpy(t.hyp, hyps + (size_t)(s0 + i) * nhyp, sizeof(double) * nhyp);
-      t.jitter = m->jitter;
-      t.NL = m->NL;
-      t.NH = m->NH;
-      t.cap = ld - 1;
-      t.ld = ld;
-      t.X = m->X;
-      t.y = m->y;
-      t.A = dv + l.o_A + (int64_t)i * ld * ld;
-      t.Linv = dv + l.o_Li + (int64_t)i * (ld / NB) * TILE;
-      t.zv = dv + l.o_zv + (int64_t)i * ld;
-      t.status = dst + i;
-      fill_desc(hd[i], &t);
+      // a scratch factor of K(hyps[s0 + i]) over the caller's rows: the descriptor fill_desc
+      // gives a model without grid, V or scratch (nothing here is owned by a model)
+      GPDesc& d = hd[i];
+      d = GPDesc{};
+      d.X = m->X;
+      d.y = m->y;
+      d.A = dv + l.o_A + (int64_t)i * ld * ld;
+      d.Linv = dv + l.o_Li + (int64_t)i * (ld / NB) * TILE;
+      d.zv = dv + l.o_zv + (int64_t)i * ld;
+      d.status = dst + i;
+      d.rsplit = 1;
+      d.ld = ld;
+      d.N = N;
+      d.NL = m->NL;
+      d.ka = 8;
+      d.ksplit = 1;
+      d.hf = derive_hyp(m->kind, hyps + (size_t)(s0 + i) * nhyp, m->jitter);
+      d.hp = d.hf;
     }
     const GPDesc* dd = nullptr;
     if ((rc = upload_slot(c, slot, cnt, &dd))) return rc;
