@@ -478,6 +478,53 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
 int mfgp_plan_ivr(mfgp_model* m, const double* w, int64_t ldw, const int64_t* cand, int64_t nc,
                   int64_t n_points, double min_gain, int refresh,
                   int64_t* cells, double* points, double* gains, int64_t* count);
+/* mfgp_plan_ivr for `count` models stepped together (a rank's Monte-Carlo seeds), with
+ * per-group quotas on the picks ("one cell per agent"). Member b gets exactly the run
+ * mfgp_plan_ivr describes, under its own weight row, candidate list, gate and stopping
+ * point; per iteration there is one pick launch, one batched 1-row append + predict (as
+ * mfgp_batch_sample_points) and one launch of each covariance-product kernel for the
+ * whole batch. A member that stopped leaves the batch step at the next chunk boundary
+ * (32 iterations; a refresh ends a chunk). The members are MFGP_F64 models of one context
+ * with their grids set, none twice; their cell counts M_b and row counts may differ, and a
+ * member without rows gives the prior's scores.
+ *   w      [count][ldw] weights, row b for member b, ldw >= the largest M_b; host or device
+ *          memory; NULL = ones.
+ *   cand, cand_off   host: the members' candidate lists one after another, member b's at
+ *          cand[cand_off[b] .. cand_off[b + 1]); cand_off has count + 1 entries, starts at 0
+ *          and does not decrease. cand NULL = all cells of every member (cand_off is not
+ *          read; member b's list is 0 .. M_b - 1 and the lists' offsets are the sums of M_b).
+ *   group, quota, ngroups   host: group is parallel to the candidate lists: position j of
+ *          member b belongs to group[offset_b + j] in [0, ngroups), ngroups in
+ *          [1, MFGP_PLAN_MAXGROUPS]. A position is allowed at a pick iff its member has made
+ *          fewer than quota[g] picks in its group so far; quota NULL = 1 each, quota[g] = 0
+ *          bars a group. A cell may stand at several positions under different groups.
+ *          group NULL = no constraint (quota must be NULL too).
+ * Among equal scores the first allowed position wins, and a NaN score never does. A
+ * member's run ends after n_points picks, before the first pick whose score is < min_gain,
+ * or when no allowed position is left. Outputs (host memory), member b's at [b][..]:
+ * cells [count][n_points], pos [count][n_points] (the chosen positions in the member's
+ * list; NULL = not wanted), points [count][n_points][2], gains [count][n_points],
+ * counts [count] the picks made. refresh as in mfgp_plan_ivr.
+ * The call settles every member as mfgp_plan_ivr does (MFGP_ERR_NOT_PD, MFGP_ERR_NO_V) and
+ * validates everything before anything is enqueued: count <= 0, a null output,
+ * n_points < 0, refresh < 0, ldw less than the largest M_b, a cell outside its member's
+ * grid, a group outside [0, ngroups), ngroups outside [1, MFGP_PLAN_MAXGROUPS] with group
+ * set, a negative quota, cand_off not monotone from 0, a non-finite weight in a host w, an
+ * MFGP_F32 member, a member without a grid, two contexts, a model twice and incremental
+ * updates disabled return MFGP_ERR_ARG, launch nothing and leave all models as they were.
+ * n_points == 0: MFGP_OK and zero counts. Afterwards, and after any error (one member's
+ * step not positive definite included), every member is as the settling left it, with
+ * mfgp_plan_ivr's guarantees: rows, predict bits and path counters as before, the loop's
+ * steps counted in mfgp_ctx_planner_stats, the next step the bits of a twin that never ran
+ * the planner. Two calls agree bit for bit. A member's sums are ordered by its own M alone,
+ * so its covariance products do not depend on the batch; its appended rows are the batch
+ * step's. */
+#define MFGP_PLAN_MAXGROUPS 64
+int mfgp_batch_plan_ivr(mfgp_model** models, int count, const double* w, int64_t ldw,
+                        const int64_t* cand, const int64_t* cand_off,
+                        const int32_t* group, const int64_t* quota, int ngroups,
+                        int64_t n_points, double min_gain, int refresh,
+                        int64_t* cells, int64_t* pos, double* points, double* gains, int64_t* counts);
 /* Keep only the first n_keep_hifi hifi rows (no refactor; benchmark reset). */
 int mfgp_truncate(mfgp_model* m, int64_t n_keep_hifi);
 /* mfgp_truncate of count models with one call (the benchmark's per-step reset). */

@@ -97,6 +97,11 @@ SIGNATURES = {
     "mfgp_plan_ivr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int64_p]),
+    "mfgp_batch_plan_ivr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "mfgp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
@@ -851,6 +856,103 @@ def batch_sample_points(models, thresholds, max_points):
     cnt = np.zeros(n, dtype=np.int64)
     check(lib().mfgp_batch_sample_points(_handles(models), n, ptr(thr), int(max_points), ptr(pts), ptr(cnt)))
     return [pts[b, :cnt[b]].copy() for b in range(n)]
+
+
+def _per_member(v, n):
+    """None, one value for all members, or one per member -> a list of n entries (None: None).
+    One per member: a list / tuple of n array-likes, or a 2-D array of n rows."""
+    if v is None:
+        return None
+    if isinstance(v, np.ndarray):
+        if v.ndim == 2:
+            if v.shape[0] != n:
+                raise ValueError(f"one row per member expected: {n} rows (got {v.shape[0]})")
+            return [v[b] for b in range(n)]
+        return [v] * n
+    v = list(v)
+    if len(v) == n and all(np.ndim(e) >= 1 for e in v):
+        return v
+    if any(np.ndim(e) >= 1 for e in v):
+        raise ValueError(f"one entry per member expected: {n} (got {len(v)})")
+    return [v] * n
+
+
+def batch_plan_ivr(models, n_points, weights=None, cand=None, groups=None, quota=None, min_gain=0.0, refresh=0):
+    """mfgp_batch_plan_ivr: the greedy integrated-variance planner (Model.plan_ivr) for every
+    model of the batch, stepped together -> a list of (cells [n_b] int64, pos [n_b] int64,
+    points [n_b, 2], gains [n_b]) per member; pos[t] is pick t's position in the member's
+    candidate list. weights: None (ones), one [>= largest M] vector for all, one per member
+    (a list or [count, >= largest M]), or a contiguous float64 device tensor [count, ld].
+    cand: None (all cells), one list for all, or one per member. groups: None (no constraint)
+    or, parallel to cand (to 0 .. M - 1 where cand is None), the group in [0, ngroups) of every
+    candidate position, one list for all or one per member; a member makes at most quota[g]
+    picks (quota None: 1) in group g. The models are unchanged; their loop is counted in
+    Context.planner_stats()."""
+    L = lib()
+    models = list(models)
+    n = len(models)
+    n_points = int(n_points)
+    Ms = [int(L.mfgp_model_m(m.handle)) for m in models]
+    maxM = max(Ms) if Ms else 0
+    keep = []   # the arrays the call reads
+    if weights is None:
+        wp, ldw = None, maxM
+    elif hasattr(weights, "data_ptr"):
+        shape, stride = tuple(weights.shape), tuple(weights.stride())
+        if str(getattr(weights, "dtype", "")).rsplit(".", 1)[-1] != "float64" or len(shape) != 2 or shape[0] != n or \
+                (shape[1] > 1 and stride[1] != 1):
+            raise ValueError("weights must be a float64 tensor [count, >= M] with contiguous rows")
+        wp, ldw = ctypes.c_void_p(int(weights.data_ptr())), int(stride[0])
+    else:
+        rows = [np.asarray(r, dtype=np.float64).reshape(-1) for r in _per_member(weights, n)]
+        ldw = max([maxM] + [r.shape[0] for r in rows])
+        wa = np.zeros((n, ldw), dtype=np.float64)
+        for b, r in enumerate(rows):
+            if r.shape[0] < Ms[b]:
+                raise ValueError(f"weights of member {b} must be [>= M] with M = {Ms[b]} (ldw = {r.shape[0]})")
+            wa[b, :r.shape[0]] = r
+        keep.append(wa)
+        wp = _addr(wa)
+    lists = _per_member(cand, n)
+    cp = op = None
+    if lists is not None:
+        lists = [np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1)) for v in lists]
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([v.shape[0] for v in lists])
+        ca = np.ascontiguousarray(np.concatenate(lists)) if n else np.zeros(0, dtype=np.int64)
+        keep += [ca, off]
+        cp, op = _addr(ca), _addr(off)
+    sizes = Ms if lists is None else [v.shape[0] for v in lists]
+    gp_, qp, ngroups = None, None, 0
+    gl = _per_member(groups, n)
+    if gl is not None:
+        gl = [np.asarray(v, dtype=np.int64).reshape(-1) for v in gl]
+        for b, v in enumerate(gl):
+            if v.shape[0] != sizes[b]:
+                raise ValueError(f"groups of member {b}: {sizes[b]} entries expected, one per candidate position "
+                                 f"(got {v.shape[0]})")
+        ga64 = np.concatenate(gl) if n else np.zeros(0, dtype=np.int64)
+        ga = np.ascontiguousarray(np.clip(ga64, -1, 2 ** 31 - 1).astype(np.int32))
+        keep.append(ga)
+        gp_ = _addr(ga)
+        if quota is not None:
+            qa = np.ascontiguousarray(np.asarray(quota, dtype=np.int64).reshape(-1))
+            keep.append(qa)
+            qp, ngroups = _addr(qa), qa.shape[0]
+        else:
+            ngroups = int(ga64.max()) + 1 if ga64.size else 1
+    elif quota is not None:
+        raise ValueError("quota needs groups")
+    P = max(n_points, 1)
+    cells = np.empty((n, P), dtype=np.int64)
+    pos = np.empty((n, P), dtype=np.int64)
+    pts = np.empty((n, P, 2), dtype=np.float64)
+    gains = np.empty((n, P), dtype=np.float64)
+    cnt = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.mfgp_batch_plan_ivr(_handles(models), n, wp, ldw, cp, op, gp_, qp, ngroups, n_points, float(min_gain),
+                                int(refresh), _addr(cells), _addr(pos), _addr(pts), _addr(gains), _addr(cnt)))
+    return [(cells[b, :cnt[b]].copy(), pos[b, :cnt[b]].copy(), pts[b, :cnt[b]].copy(), gains[b, :cnt[b]].copy())
+            for b in range(n)]
 
 
 def batch_predict(models, mu_ptr, var_ptr, asynchronous=False):

@@ -40,6 +40,19 @@
 // Every kernel of the loop is a no-op once the gate is closed. No atomics, no flags, no
 // cross-workgroup hand-offs, no calls: everything meets at launch boundaries.
 //
+// The batched forms (mfgp_batch_plan_ivr: k_ivr_pick_batch, k_plan_x_batch, k_cov_dot_batch,
+// k_cov_psum_batch, k_kss_t_batch, k_kss_out_batch, k_cov_apply_batch) serve every member
+// of a batch of models with one launch each per pick. The member is the slowest grid
+// dimension; its arguments (PlanMember: what the single forms take by value) sit in a
+// device array the workgroup reads uniformly, with the member's row count before the run,
+// so the array serves a chunk of iterations and the iteration's index is the only
+// argument that changes. The grids are the largest member's, and a workgroup past its own
+// member's cells or rows exits. Each kernel and its batched form call one __forceinline__
+// body, so a member's order of sums is the single form's and depends on its own M alone.
+// The batched pick also masks the positions of exhausted groups (a per-member array of
+// group counters against the quotas) and records the chosen position. k_plan_scatter is
+// k_plan_ssum's body with a candidate list: S at the candidates' cells only.
+//
 // Order of sums. Pass A: thread (wave wv, lane) owns the cell pair lane & 31 of every tile
 // of the segment and the rows 8 k + 2 wv + (lane >> 5) of the chunk; for a row it adds the
 // tiles' products in tile order (one fused multiply-add chain per cell of the pair), adds
@@ -72,12 +85,13 @@ __device__ __forceinline__ int pair_cells(int64_t c0, int64_t M) {
 // ---- pass A -------------------------------------------------------------------------------
 constexpr int COV_U = 4;   // rows in flight per thread (each COV_SEG 16-byte loads)
 
-__global__ __launch_bounds__(NT) void k_cov_dot(const CovApply a) {
+// workgroup (bx: cell segment, by: chunk of rows) of pass A
+__device__ __forceinline__ void cov_dot_body(const CovApply& a, unsigned bx, unsigned by) {
   if (gate_closed(a.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int hh = lane >> 5, cp = lane & 31;
-  const int64_t t0 = (int64_t)blockIdx.x * COV_SEG;
-  const int64_t r0 = (int64_t)blockIdx.y * COV_RC;
+  const int64_t t0 = (int64_t)bx * COV_SEG;
+  const int64_t r0 = (int64_t)by * COV_RC;
   dv2 xs[COV_SEG];
   int nv[COV_SEG];
 #pragma unroll
@@ -108,18 +122,43 @@ __global__ __launch_bounds__(NT) void k_cov_dot(const CovApply a) {
       double r = sx + sy;
 #pragma unroll
       for (int off = 16; off > 0; off >>= 1) r = r + __shfl_xor(r, off);
-      if (cp == 0 && n < a.N) gp(a.part)[(int64_t)blockIdx.x * a.pld + n] = r;
+      if (cp == 0 && n < a.N) gp(a.part)[(int64_t)bx * a.pld + n] = r;
     }
   }
 }
 
-__global__ __launch_bounds__(NT) void k_cov_psum(const CovApply a, int nseg) {
+__global__ __launch_bounds__(NT) void k_cov_dot(const CovApply a) { cov_dot_body(a, blockIdx.x, blockIdx.y); }
+
+// The batched forms (mfgp_batch_plan_ivr): member blockIdx.z of the device array ms, its
+// product's arguments with the rows appended up to iteration `it`. The grids are the
+// largest member's: a workgroup past its own member's cells or rows exits.
+__device__ __forceinline__ CovApply member_apply(const PlanMember& m, int64_t it) {
+  CovApply a = m.a;
+  a.N += it + 1;
+  return a;
+}
+
+__global__ __launch_bounds__(NT) void k_cov_dot_batch(const PlanMember* __restrict__ ms, int64_t it) {
+  const PlanMember& m = ms[blockIdx.z];
+  const CovApply a = member_apply(m, it);
+  if ((int)blockIdx.x >= m.nseg || (int64_t)blockIdx.y * COV_RC >= a.N) return;
+  cov_dot_body(a, blockIdx.x, blockIdx.y);
+}
+
+__device__ __forceinline__ void cov_psum_body(const CovApply& a, int nseg, unsigned bx) {
   if (gate_closed(a.gate)) return;
-  const int64_t n = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const int64_t n = (int64_t)bx * NT + threadIdx.x;
   if (n >= a.N) return;
   double s = 0.0;
   for (int sg = 0; sg < nseg; ++sg) s = s + gp(a.part)[(int64_t)sg * a.pld + n];
   gp(a.p)[n] = s;
+}
+
+__global__ __launch_bounds__(NT) void k_cov_psum(const CovApply a, int nseg) { cov_psum_body(a, nseg, blockIdx.x); }
+
+__global__ __launch_bounds__(NT) void k_cov_psum_batch(const PlanMember* __restrict__ ms, int64_t it) {
+  const PlanMember& m = ms[blockIdx.y];
+  cov_psum_body(member_apply(m, it), m.nseg, blockIdx.x);
 }
 
 // ---- the separable K** x ---------------------------------------------------------------------
@@ -149,11 +188,11 @@ __global__ __launch_bounds__(NT) void k_kss_axes(const KssArgs k) {
 }
 
 // T[part][ix][iy] = sum_iy' Ky_part[iy][iy'] x(ix, iy'), iy' ascending
-__global__ __launch_bounds__(NT) void k_kss_t(const KssArgs k, const double* __restrict__ x, double* __restrict__ T,
-                                              const int* gate) {
+__device__ __forceinline__ void kss_t_body(const KssArgs& k, const double* __restrict__ x, double* __restrict__ T,
+                                           const int* gate, unsigned bx) {
   if (gate_closed(gate)) return;
   const int64_t Mc = (int64_t)k.nx * k.ny;
-  const int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const int64_t e = (int64_t)bx * NT + threadIdx.x;
   if (e >= Mc * k.parts) return;
   const int part = (int)(e / Mc);
   const int64_t r = e % Mc, ix = r / k.ny, iy = r % k.ny;
@@ -164,12 +203,24 @@ __global__ __launch_bounds__(NT) void k_kss_t(const KssArgs k, const double* __r
   gp(T)[e] = s;
 }
 
+__global__ __launch_bounds__(NT) void k_kss_t(const KssArgs k, const double* __restrict__ x, double* __restrict__ T,
+                                              const int* gate) {
+  kss_t_body(k, x, T, gate, blockIdx.x);
+}
+
+// (a member on the general K** x form has no part in either launch)
+__global__ __launch_bounds__(NT) void k_kss_t_batch(const PlanMember* __restrict__ ms) {
+  const PlanMember& m = ms[blockIdx.y];
+  if (!m.sep) return;
+  kss_t_body(m.k, m.a.x, m.T, m.a.gate, blockIdx.x);
+}
+
 // out(ix, iy) = sum_part s_part sum_ix' Kx_part[ix][ix'] T[part][ix'][iy], ix' ascending, part L then H
-__global__ __launch_bounds__(NT) void k_kss_out(const KssArgs k, const double* __restrict__ T, double* __restrict__ out,
-                                                const int* gate) {
+__device__ __forceinline__ void kss_out_body(const KssArgs& k, const double* __restrict__ T, double* __restrict__ out,
+                                             const int* gate, unsigned bx) {
   if (gate_closed(gate)) return;
   const int64_t Mc = (int64_t)k.nx * k.ny;
-  const int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const int64_t e = (int64_t)bx * NT + threadIdx.x;
   if (e >= Mc) return;
   const int64_t ix = e / k.ny, iy = e % k.ny;
   double res = 0.0;
@@ -185,15 +236,25 @@ __global__ __launch_bounds__(NT) void k_kss_out(const KssArgs k, const double* _
   gp(out)[ix * k.sx + iy * k.sy] = res;
 }
 
+__global__ __launch_bounds__(NT) void k_kss_out(const KssArgs k, const double* __restrict__ T, double* __restrict__ out,
+                                                const int* gate) {
+  kss_out_body(k, T, out, gate, blockIdx.x);
+}
+
+__global__ __launch_bounds__(NT) void k_kss_out_batch(const PlanMember* __restrict__ ms) {
+  const PlanMember& m = ms[blockIdx.y];
+  if (!m.sep) return;
+  kss_out_body(m.k, m.T, m.kxo, m.a.gate, blockIdx.x);
+}
+
 // ---- pass B -------------------------------------------------------------------------------
 constexpr int COVB_U = 8;   // rows in flight per thread
 
-__global__ __launch_bounds__(NT) void k_cov_apply(const CovApply a) {
-  __shared__ double red[2][8][PBM];
+// workgroup of tile t; red: the workgroup's LDS [2][8][PBM]
+__device__ __forceinline__ void cov_apply_body(const CovApply& a, int64_t t, double (*red)[8][PBM]) {
   if (gate_closed(a.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int hh = lane >> 5, cp = lane & 31, rg = 2 * wv + hh;
-  const int64_t t = blockIdx.x;
   const int64_t c0 = t * PBM + 2 * cp;
   const int nv = pair_cells(c0, a.M);
   const GLOBAL double* pv = gp(a.V) + t * a.vld * PBM + 2 * cp;
@@ -262,16 +323,27 @@ __global__ __launch_bounds__(NT) void k_cov_apply(const CovApply a) {
   }
 }
 
+__global__ __launch_bounds__(NT) void k_cov_apply(const CovApply a) {
+  __shared__ double red[2][8][PBM];
+  cov_apply_body(a, blockIdx.x, red);
+}
+
+__global__ __launch_bounds__(NT) void k_cov_apply_batch(const PlanMember* __restrict__ ms, int64_t it) {
+  __shared__ double red[2][8][PBM];
+  const PlanMember& m = ms[blockIdx.y];
+  if ((int64_t)blockIdx.x * PBM >= m.a.M) return;
+  cov_apply_body(member_apply(m, it), blockIdx.x, red);
+}
+
 // ---- the planner's kernels -------------------------------------------------------------------
 // g = row `row` of V, x = w o g, tau_part[workgroup] = sum over its 256 cells of w g^2
-__global__ __launch_bounds__(NT) void k_plan_x(const double* __restrict__ V, int64_t vld, int64_t row, int64_t M,
-                                               const double* __restrict__ w, double* __restrict__ g,
-                                               double* __restrict__ x, double* __restrict__ tau_part,
-                                               const int* gate) {
-  __shared__ double red[NT];
+__device__ __forceinline__ void plan_x_body(const double* __restrict__ V, int64_t vld, int64_t row, int64_t M,
+                                            const double* __restrict__ w, double* __restrict__ g,
+                                            double* __restrict__ x, double* __restrict__ tau_part, const int* gate,
+                                            unsigned bx, double* red) {
   if (gate_closed(gate)) return;
   const int tid = threadIdx.x;
-  const int64_t c = (int64_t)blockIdx.x * NT + tid;
+  const int64_t c = (int64_t)bx * NT + tid;
   double tw = 0.0;
   if (c < M) {
 #pragma clang fp contract(off)
@@ -288,22 +360,52 @@ __global__ __launch_bounds__(NT) void k_plan_x(const double* __restrict__ V, int
     if (tid < s) red[tid] = red[tid] + red[tid + s];
     __syncthreads();
   }
-  if (tid == 0) gp(tau_part)[blockIdx.x] = red[0];
+  if (tid == 0) gp(tau_part)[bx] = red[0];
 }
 
-// S[c] = k_ivr_partial's numerators partial[segment][c] (nw = 1, all M cells) added in segment order
+__global__ __launch_bounds__(NT) void k_plan_x(const double* __restrict__ V, int64_t vld, int64_t row, int64_t M,
+                                               const double* __restrict__ w, double* __restrict__ g,
+                                               double* __restrict__ x, double* __restrict__ tau_part,
+                                               const int* gate) {
+  __shared__ double red[NT];
+  plan_x_body(V, vld, row, M, w, g, x, tau_part, gate, blockIdx.x, red);
+}
+
+// (the row iteration `it` appended: a.N + it)
+__global__ __launch_bounds__(NT) void k_plan_x_batch(const PlanMember* __restrict__ ms, int64_t it) {
+  __shared__ double red[NT];
+  const PlanMember& m = ms[blockIdx.y];
+  const CovApply& a = m.a;
+  if ((int64_t)blockIdx.x * NT >= a.M) return;
+  plan_x_body(a.V, a.vld, a.N + it, a.M, m.w, const_cast<double*>(a.g), const_cast<double*>(a.x),
+              const_cast<double*>(a.tau_part), a.gate, blockIdx.x, red);
+}
+
+// S[cand[j]] (cand null: S[j]) = k_ivr_partial's numerators partial[segment][j] (nw = 1, j < nc)
+// added in segment order. A cell listed twice receives the same bits twice.
+__device__ __forceinline__ void plan_ssum_body(const double* __restrict__ partial, int nseg, int64_t nc,
+                                               const int64_t* __restrict__ cand, double* __restrict__ S) {
+  const int64_t j = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (j >= nc) return;
+  double s = 0.0;
+  for (int sg = 0; sg < nseg; ++sg) s = s + gp(partial)[(int64_t)sg * nc + j];
+  gp(S)[cand ? gp(cand)[j] : j] = s;
+}
+
+// S[c] = the numerators of all M cells
 __global__ __launch_bounds__(NT) void k_plan_ssum(const double* __restrict__ partial, int nseg, int64_t M,
                                                   double* __restrict__ S) {
-  const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
-  if (c >= M) return;
-  double s = 0.0;
-  for (int sg = 0; sg < nseg; ++sg) s = s + gp(partial)[(int64_t)sg * M + c];
-  gp(S)[c] = s;
+  plan_ssum_body(partial, nseg, M, nullptr, S);
 }
 
-__global__ __launch_bounds__(NT) void k_ivr_pick(const PlanPick q) {
-  __shared__ double rv[4];
-  __shared__ int64_t ri[4];
+__global__ __launch_bounds__(NT) void k_plan_scatter(const double* __restrict__ partial, int nseg, int64_t nc,
+                                                     const int64_t* __restrict__ cand, double* __restrict__ S) {
+  plan_ssum_body(partial, nseg, nc, cand, S);
+}
+
+// One workgroup's pick for one model. q.group set (the batched planner): position j is
+// allowed while its group has made fewer picks than its quota.
+__device__ __forceinline__ void ivr_pick_body(const PlanPick& q, double* rv, int64_t* ri) {
   int* gate = reinterpret_cast<int*>(q.state);
   if (*gp(gate) == 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -316,6 +418,10 @@ __global__ __launch_bounds__(NT) void k_ivr_pick(const PlanPick q) {
   int64_t bi = INT64_MAX;
   for (int64_t j = tid; j < q.nc; j += NT) {
 #pragma clang fp contract(off)
+    if (q.group) {
+      const int gj = gp(q.group)[j];
+      if (gp(q.gcount)[gj] >= (q.quota ? gp(q.quota)[gj] : 1)) continue;
+    }
     const int64_t c = q.cand ? gp(q.cand)[j] : j;
     const double dc = (gp(q.var)[c] + q.noise) + q.jitter;
     argmax_pair(bv, bi, div_(gp(q.S)[c], dc), j);
@@ -342,7 +448,25 @@ __global__ __launch_bounds__(NT) void k_ivr_pick(const PlanPick q) {
   gp(q.gains)[cnt] = bv;
   gp(q.pts)[2 * cnt] = gx;
   gp(q.pts)[2 * cnt + 1] = gy;
+  if (q.pos) gp(q.pos)[cnt] = bi;
+  if (q.group) {
+    const int gb = gp(q.group)[bi];
+    gp(q.gcount)[gb] = gp(q.gcount)[gb] + 1;
+  }
   gp(q.state)[1] = cnt + 1;
+}
+
+__global__ __launch_bounds__(NT) void k_ivr_pick(const PlanPick q) {
+  __shared__ double rv[4];
+  __shared__ int64_t ri[4];
+  ivr_pick_body(q, rv, ri);
+}
+
+// one workgroup per member
+__global__ __launch_bounds__(NT) void k_ivr_pick_batch(const PlanMember* __restrict__ ms) {
+  __shared__ double rv[4];
+  __shared__ int64_t ri[4];
+  ivr_pick_body(ms[blockIdx.x].q, rv, ri);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
@@ -389,8 +513,41 @@ hipError_t launch_plan_ssum(const double* partial, int nseg, int64_t M, double* 
   return last();
 }
 
+hipError_t launch_plan_scatter(const double* partial, int nseg, int64_t nc, const int64_t* cand, double* S,
+                               hipStream_t s) {
+  if (nc <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_plan_scatter, dim3((unsigned)((nc + NT - 1) / NT)), dim3(NT), 0, s, partial, nseg, nc, cand, S);
+  return last();
+}
+
 hipError_t launch_ivr_pick(const PlanPick& q, hipStream_t s) {
   hipLaunchKernelGGL(k_ivr_pick, dim3(1), dim3(NT), 0, s, q);
+  return last();
+}
+
+hipError_t launch_ivr_pick_batch(const PlanMember* ms, int count, hipStream_t s) {
+  hipLaunchKernelGGL(k_ivr_pick_batch, dim3((unsigned)count), dim3(NT), 0, s, ms);
+  return last();
+}
+
+hipError_t launch_plan_update_batch(const PlanMember* ms, int count, int64_t it, int64_t maxM, int64_t maxN,
+                                    bool any_sep, hipStream_t s) {
+  const unsigned B = (unsigned)count, wgM = (unsigned)((maxM + NT - 1) / NT);
+  hipError_t e;
+  hipLaunchKernelGGL(k_plan_x_batch, dim3((unsigned)plan_tau_parts(maxM), B), dim3(NT), 0, s, ms, it);
+  if ((e = last()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_cov_dot_batch, dim3((unsigned)cov_segments(maxM), (unsigned)((maxN + COV_RC - 1) / COV_RC), B),
+                     dim3(NT), 0, s, ms, it);
+  if ((e = last()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_cov_psum_batch, dim3((unsigned)((maxN + NT - 1) / NT), B), dim3(NT), 0, s, ms, it);
+  if ((e = last()) != hipSuccess) return e;
+  if (any_sep) {
+    hipLaunchKernelGGL(k_kss_t_batch, dim3(2 * wgM, B), dim3(NT), 0, s, ms);   // (up to two parts)
+    if ((e = last()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_kss_out_batch, dim3(wgM, B), dim3(NT), 0, s, ms);
+    if ((e = last()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_cov_apply_batch, dim3((unsigned)ntiles_grid(maxM), B), dim3(NT), 0, s, ms, it);
   return last();
 }
 

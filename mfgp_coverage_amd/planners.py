@@ -24,6 +24,9 @@ takes it); each model stops at its own threshold.
 criterion instead of the maximal variance (libmfgp_hip's mfgp_plan_ivr, DESIGN.md
 section 21): the same in-place loop, each pick scored by a rank-one update from one
 product of the posterior covariance with a grid vector.
+``compute_sample_points_ivr_batch`` runs it for many models at once, one launch of each
+kind per pick for the whole batch, with per-group quotas on the picks ("one cell per
+agent"; libmfgp_hip's mfgp_batch_plan_ivr).
 
 On any error (a step that is not positive definite raises LinAlgError, as updt /
 updt_hifi does inside the reference's loop) the models are as before the call, and
@@ -104,3 +107,43 @@ def compute_sample_points_ivr(model, x_star, n_points, weights=None, candidates=
     model._grid_to_device(xs)
     _, pts, gains = model._dev().plan_ivr(n_points, weights, candidates, min_gain, refresh)
     return pts, gains
+
+
+def compute_sample_points_ivr_batch(models, x_star, n_points, weights=None, candidates=None, groups=None, quota=None,
+                                    min_gain=0.0, refresh=0):
+    """``compute_sample_points_ivr`` for every model of ``models`` (one context, the same
+    grid ``x_star``), stepped together, with per-group quotas on the picks (libmfgp_hip's
+    mfgp_batch_plan_ivr) -> a list of ``(points [n_b, 2], gains [n_b],
+    groups_of_picks)`` per model. ``weights``: None (ones), one [M] vector for all, or one per
+    model; ``candidates``: the allowed rows of ``x_star``, None (all), one list for all, or one
+    per model; ``groups``: None (no constraint, ``groups_of_picks`` is None) or the group of
+    every candidate position (of every row of ``x_star`` where ``candidates`` is None), one
+    list for all or one per model -- a model then makes at most ``quota[g]`` picks (None: one)
+    in group g, "one cell per agent", and ``groups_of_picks[t]`` is the group pick t was taken
+    for. Each model stops at its own ``min_gain`` crossing, after ``n_points`` picks or when
+    no allowed position is left, and is unchanged. Not available on precision="f32" models
+    (TypeError)."""
+    from . import _lib
+    if not models:
+        return []
+    for m in models:
+        if not isinstance(m, (SFGP, MFGP)):
+            raise TypeError("Invalid model type: must be SFGP or MFGP")
+    for m in models:
+        if m._dev().dtype != _lib.F64:
+            raise TypeError("compute_sample_points_ivr_batch needs the fp64 resident V: not available on "
+                            "precision='f32' models")
+    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
+    for m in models:
+        m._sync_data()
+        m._push_hyp()
+        m._grid_to_device(xs)
+    n = len(models)
+    runs = _lib.batch_plan_ivr([m._dev() for m in models], n_points, weights, candidates, groups, quota, min_gain,
+                               refresh)
+    gl = _lib._per_member(groups, n)
+    out = []
+    for b, (_, pos, pts, gains) in enumerate(runs):
+        picked = None if gl is None else np.asarray(gl[b], dtype=np.int64).reshape(-1)[pos]
+        out.append((pts, gains, picked))
+    return out
