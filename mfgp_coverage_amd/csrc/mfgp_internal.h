@@ -295,7 +295,7 @@ hipError_t launch_ivr_partial(const GPDesc& d, const int64_t* cand, int64_t nc, 
 constexpr int COV_SEG = 8;    // 64-cell tiles per cell segment of k_cov_dot (one partial of p each)
 constexpr int COV_RC = 64;    // training rows per k_cov_dot workgroup
 inline int64_t cov_segments(int64_t M) { return (ntiles_grid(M) + COV_SEG - 1) / COV_SEG; }
-inline int64_t plan_tau_parts(int64_t M) { return (M + NT - 1) / NT; }   // k_plan_x workgroups
+inline int64_t plan_tau_parts(int64_t M) { return (M + NT - 1) / NT; }   // k_plan_x_batch workgroups per member
 constexpr int KSS_AXIS_MAX = 256;   // longest lattice axis the separable K** x serves
 struct CovApply {
   const double* V;        // resident V [tiles][vld][64]
@@ -341,15 +341,14 @@ struct PlanPick {
   int64_t* cells;         // [n_points]
   double* gains;          // [n_points]
   double* pts;            // [n_points][2]
-  // the quota-constrained form (mfgp_batch_plan_ivr); group null: every position is allowed
+  // the quotas (group null: every position is allowed)
   const int32_t* group;   // [nc] the group of each candidate position
   const int64_t* quota;   // [groups] picks allowed per group, or null = 1 each
   int64_t* gcount;        // [groups] this run's picks per group so far
   int64_t* pos;           // [n_points] the chosen positions in the candidate list, or null
 };
-// One member of the batched planner's iteration (mfgp_batch_plan_ivr): what the single
-// planner passes by value, in a device array the workgroups of member blockIdx.z read
-// uniformly. a.N is the member's row count before the run: iteration `it` appends row
+// One member of the planner's iteration (plan_ivr_run; mfgp_plan_ivr is the batch of one):
+// its arguments in a device array the workgroups of member blockIdx.z read uniformly. a.N is the member's row count before the run: iteration `it` appends row
 // a.N + it, so an array serves a whole chunk of iterations.
 struct PlanMember {
   CovApply a;             // (a.kx = kxo where sep, else null)
@@ -365,17 +364,13 @@ hipError_t launch_kss_axes(const KssArgs& k, hipStream_t s);
 // T: scratch [parts][nx * ny]
 hipError_t launch_kss(const KssArgs& k, const double* x, double* T, double* out, const int* gate, hipStream_t s);
 hipError_t launch_cov_apply(const CovApply& a, hipStream_t s);
-hipError_t launch_plan_x(const double* V, int64_t vld, int64_t row, int64_t M, const double* w, double* g, double* x,
-                         double* tau_part, const int* gate, hipStream_t s);
-hipError_t launch_plan_ssum(const double* partial, int nseg, int64_t M, double* S, hipStream_t s);
-// the candidate-list form: S[cand[j]] = the segments' partial[segment][j] in order, j < nc
+// S[cand[j]] (cand null: S[j]) = the segments' partial[segment][j] in order, j < nc
 hipError_t launch_plan_scatter(const double* partial, int nseg, int64_t nc, const int64_t* cand, double* S,
                                hipStream_t s);
-hipError_t launch_ivr_pick(const PlanPick& q, hipStream_t s);
-// The batched planner's launches for `count` members (ms: device array): every member's pick
+// The planner's launches for `count` members (ms: device array): every member's pick
 // in one launch, and after the batch step iteration it's rank-one update of every member's
-// numerators -- k_plan_x, k_cov_dot, k_cov_psum, k_kss_t / k_kss_out (any_sep), k_cov_apply,
-// one launch each, grids sized by maxM cells and maxN rows (the largest member's, rows as
+// numerators -- the _batch forms of k_plan_x, k_cov_dot, k_cov_psum, k_kss_t / k_kss_out (any_sep)
+// and k_cov_apply, one launch each, grids sized by maxM cells and maxN rows (the largest member's, rows as
 // of this iteration).
 hipError_t launch_ivr_pick_batch(const PlanMember* ms, int count, hipStream_t s);
 hipError_t launch_plan_update_batch(const PlanMember* ms, int count, int64_t it, int64_t maxM, int64_t maxN,

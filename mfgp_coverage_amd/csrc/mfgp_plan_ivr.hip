@@ -23,7 +23,8 @@
 //                with cov_pt / cov_entry(.., 0.0) evaluated on the fly: M^2 exps. The
 //                stand-alone form stores u; the planner's form updates the numerators S.
 //
-// The planner (mfgp_plan_ivr, mfgp_planners.hip). With weights w, C_t the covariance
+// The planner (plan_ivr_run in mfgp_planners.hip: one loop behind mfgp_batch_plan_ivr and,
+// as its batch of one, mfgp_plan_ivr). For one member, with weights w, C_t the covariance
 // after t picks and S_t(c) = sum_i w_i C_t(i,c)^2, picking c* as a hifi row gives
 // C_{t+1} = C_t - g g^T, g(i) = C_t(i,c*) / sqrt(C_t(c*,c*) + sigma_H + jitter): the row
 // the one-row bordered append stores as row N + t of V. With x = w o g, tau = sum_i w_i g_i^2
@@ -31,27 +32,29 @@
 //   S_{t+1}(c) = S_t(c) - 2 g(c) u(c) - g(c)^2 tau
 //   score_{t+1}(c) = S_{t+1}(c) / (var_{t+1}(c) + sigma_H + jitter)
 //
-//   k_ivr_pick   one workgroup: the argmax of the score over the allowed cells
-//                (argmax_pair's rule), the chosen cell's coordinates and posterior mean as
-//                the next hifi row, (cell, gain) recorded, the device gate closed at the
+//   k_ivr_pick_batch  one workgroup per member: the argmax of the score over the allowed
+//                positions of its list (argmax_pair's rule; a position of an exhausted
+//                group -- a per-member array of group counters against the quotas -- is
+//                masked), the chosen cell's coordinates and posterior mean as the next
+//                hifi row, (cell, position, gain) recorded, the device gate closed at the
 //                end of the run (as k_choi_select).
-//   k_plan_x     after the step: g = row N + t of V, x = w o g, tau's partial sums.
-//   k_plan_ssum  S from k_ivr_partial's numerators: the segments in order, undivided.
+//   k_plan_x_batch  after the step: g = row N + t of V, x = w o g, tau's partial sums.
+//   k_plan_scatter  S from k_ivr_partial's numerators over the member's list: the segments
+//                in order, undivided, stored at the candidates' cells only.
 // Every kernel of the loop is a no-op once the gate is closed. No atomics, no flags, no
 // cross-workgroup hand-offs, no calls: everything meets at launch boundaries.
 //
-// The batched forms (mfgp_batch_plan_ivr: k_ivr_pick_batch, k_plan_x_batch, k_cov_dot_batch,
-// k_cov_psum_batch, k_kss_t_batch, k_kss_out_batch, k_cov_apply_batch) serve every member
-// of a batch of models with one launch each per pick. The member is the slowest grid
-// dimension; its arguments (PlanMember: what the single forms take by value) sit in a
-// device array the workgroup reads uniformly, with the member's row count before the run,
-// so the array serves a chunk of iterations and the iteration's index is the only
-// argument that changes. The grids are the largest member's, and a workgroup past its own
-// member's cells or rows exits. Each kernel and its batched form call one __forceinline__
-// body, so a member's order of sums is the single form's and depends on its own M alone.
-// The batched pick also masks the positions of exhausted groups (a per-member array of
-// group counters against the quotas) and records the chosen position. k_plan_scatter is
-// k_plan_ssum's body with a candidate list: S at the candidates' cells only.
+// The loop's kernels are the batched forms (k_ivr_pick_batch, k_plan_x_batch,
+// k_cov_dot_batch, k_cov_psum_batch, k_kss_t_batch, k_kss_out_batch, k_cov_apply_batch):
+// they serve every member of a batch of models with one launch each per pick. The member
+// is the slowest grid dimension; its arguments (PlanMember) sit in a device array the
+// workgroup reads uniformly, with the member's row count before the run, so the array
+// serves a chunk of iterations and the iteration's index is the only argument that
+// changes. The grids are the largest member's, and a workgroup past its own member's
+// cells or rows exits. The covariance product's kernels also have by-value forms
+// (k_cov_dot, k_cov_psum, k_kss_t, k_kss_out, k_cov_apply: mfgp_cov_apply's); each pair
+// calls one __forceinline__ body, so a member's order of sums is the stand-alone
+// product's and depends on its own M alone.
 //
 // Order of sums. Pass A: thread (wave wv, lane) owns the cell pair lane & 31 of every tile
 // of the segment and the rows 8 k + 2 wv + (lane >> 5) of the chunk; for a row it adds the
@@ -129,7 +132,7 @@ __device__ __forceinline__ void cov_dot_body(const CovApply& a, unsigned bx, uns
 
 __global__ __launch_bounds__(NT) void k_cov_dot(const CovApply a) { cov_dot_body(a, blockIdx.x, blockIdx.y); }
 
-// The batched forms (mfgp_batch_plan_ivr): member blockIdx.z of the device array ms, its
+// The planner's forms (plan_ivr_run): member blockIdx.z of the device array ms, its
 // product's arguments with the rows appended up to iteration `it`. The grids are the
 // largest member's: a workgroup past its own member's cells or rows exits.
 __device__ __forceinline__ CovApply member_apply(const PlanMember& m, int64_t it) {
@@ -363,14 +366,6 @@ __device__ __forceinline__ void plan_x_body(const double* __restrict__ V, int64_
   if (tid == 0) gp(tau_part)[bx] = red[0];
 }
 
-__global__ __launch_bounds__(NT) void k_plan_x(const double* __restrict__ V, int64_t vld, int64_t row, int64_t M,
-                                               const double* __restrict__ w, double* __restrict__ g,
-                                               double* __restrict__ x, double* __restrict__ tau_part,
-                                               const int* gate) {
-  __shared__ double red[NT];
-  plan_x_body(V, vld, row, M, w, g, x, tau_part, gate, blockIdx.x, red);
-}
-
 // (the row iteration `it` appended: a.N + it)
 __global__ __launch_bounds__(NT) void k_plan_x_batch(const PlanMember* __restrict__ ms, int64_t it) {
   __shared__ double red[NT];
@@ -392,18 +387,12 @@ __device__ __forceinline__ void plan_ssum_body(const double* __restrict__ partia
   gp(S)[cand ? gp(cand)[j] : j] = s;
 }
 
-// S[c] = the numerators of all M cells
-__global__ __launch_bounds__(NT) void k_plan_ssum(const double* __restrict__ partial, int nseg, int64_t M,
-                                                  double* __restrict__ S) {
-  plan_ssum_body(partial, nseg, M, nullptr, S);
-}
-
 __global__ __launch_bounds__(NT) void k_plan_scatter(const double* __restrict__ partial, int nseg, int64_t nc,
                                                      const int64_t* __restrict__ cand, double* __restrict__ S) {
   plan_ssum_body(partial, nseg, nc, cand, S);
 }
 
-// One workgroup's pick for one model. q.group set (the batched planner): position j is
+// One workgroup's pick for one model. q.group set: position j is
 // allowed while its group has made fewer picks than its quota.
 __device__ __forceinline__ void ivr_pick_body(const PlanPick& q, double* rv, int64_t* ri) {
   int* gate = reinterpret_cast<int*>(q.state);
@@ -456,12 +445,6 @@ __device__ __forceinline__ void ivr_pick_body(const PlanPick& q, double* rv, int
   gp(q.state)[1] = cnt + 1;
 }
 
-__global__ __launch_bounds__(NT) void k_ivr_pick(const PlanPick q) {
-  __shared__ double rv[4];
-  __shared__ int64_t ri[4];
-  ivr_pick_body(q, rv, ri);
-}
-
 // one workgroup per member
 __global__ __launch_bounds__(NT) void k_ivr_pick_batch(const PlanMember* __restrict__ ms) {
   __shared__ double rv[4];
@@ -501,27 +484,10 @@ hipError_t launch_cov_apply(const CovApply& a, hipStream_t s) {
   return last();
 }
 
-hipError_t launch_plan_x(const double* V, int64_t vld, int64_t row, int64_t M, const double* w, double* g, double* x,
-                         double* tau_part, const int* gate, hipStream_t s) {
-  hipLaunchKernelGGL(k_plan_x, dim3((unsigned)plan_tau_parts(M)), dim3(NT), 0, s, V, vld, row, M, w, g, x, tau_part,
-                     gate);
-  return last();
-}
-
-hipError_t launch_plan_ssum(const double* partial, int nseg, int64_t M, double* S, hipStream_t s) {
-  hipLaunchKernelGGL(k_plan_ssum, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, s, partial, nseg, M, S);
-  return last();
-}
-
 hipError_t launch_plan_scatter(const double* partial, int nseg, int64_t nc, const int64_t* cand, double* S,
                                hipStream_t s) {
   if (nc <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_plan_scatter, dim3((unsigned)((nc + NT - 1) / NT)), dim3(NT), 0, s, partial, nseg, nc, cand, S);
-  return last();
-}
-
-hipError_t launch_ivr_pick(const PlanPick& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_ivr_pick, dim3(1), dim3(NT), 0, s, q);
   return last();
 }
 

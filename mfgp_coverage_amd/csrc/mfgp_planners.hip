@@ -1,8 +1,9 @@
-// The planners of libmfgp_hip.so: the four loops that run on the caller's models in
+// The planners of libmfgp_hip.so: the loops that run on the caller's models in
 // place -- the sample-point loops (mfgp_sample_points, mfgp_batch_sample_points) and the
-// greedy integrated-variance planners (mfgp_plan_ivr, mfgp_batch_plan_ivr), all over the
-// batch step and on one scaffold (PlanRun: enter, grow, chunk_end, finish, and fail on
-// every error path) -- and the host side of the Voronoi-cell reductions (mfgp_cells.hip).
+// greedy integrated-variance planner (plan_ivr_run: one loop with two entry points,
+// mfgp_batch_plan_ivr and, as its batch of one, mfgp_plan_ivr), all over the batch step
+// and on one scaffold (PlanRun: enter, grow, chunk_end, finish, and fail on every error
+// path) -- and the host side of the Voronoi-cell reductions (mfgp_cells.hip).
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -228,6 +229,274 @@ struct __attribute__((visibility("hidden"))) PlanRun {   // (its members: no sym
     return rc ? rc : sync;
   }
 };
+
+// The greedy integrated-variance planner (mfgp_plan_ivr.hip) behind both of its entry
+// points: for each model of a batch stepped together, n_points cells chosen one after
+// another, each the allowed cell whose measurement lowers the weighted posterior variance
+// of the model's whole grid most, given the picks before it, with per-group quotas on the
+// picks. mfgp_plan_ivr is the batch of one (`single`: its own texts and order where its
+// checks differ, and its nc counts with a NULL list too). Per iteration: ONE
+// k_ivr_pick_batch (every live member's masked argmax of S / (var + sigma_H + jitter), the
+// cell and its posterior mean as its next hifi row at its place in xn / yn, or its gate
+// closed), ONE batch step of one row each (as mfgp_batch_sample_points calls it: the
+// lattice step where its gates take it, else the fused V stream) and, for the rank-one
+// update of the numerators S from one covariance product over the resident V, ONE launch
+// each of k_plan_x_batch, k_cov_dot_batch, k_cov_psum_batch, k_kss_t_batch, k_kss_out_batch
+// and k_cov_apply_batch, which read each member's arguments from a device array uploaded
+// once per chunk (the row count of an iteration is the member's own plus the iteration's
+// index). S_0, and S again every `refresh` picks, is k_ivr_partial per member over its
+// candidate list -- the only GEMM -- scattered into S at the candidates' cells: no other
+// cell of S is read. Chunks of iterations are enqueued behind the device gates with one
+// status read per chunk, on the caller's models (plan_enter / plan_leave); a chunk ends
+// where a refresh is due. A member that stopped leaves the batch at the next chunk
+// boundary; its kernels are no-ops behind its gate meanwhile.
+static int plan_ivr_run(const char* who, bool single, mfgp_model* const* t, int count, const double* w, int64_t ldw,
+                        const int64_t* cand, const int64_t* cand_off, const int32_t* group, const int64_t* quota,
+                        int ngroups, int64_t n_points, double min_gain, int refresh, int64_t* cells, int64_t* pos,
+                        double* points, double* gains, int64_t* counts) {
+  if (n_points < 0) return set_err(MFGP_ERR_ARG, "%s: negative n_points", who);
+  if (refresh < 0) return set_err(MFGP_ERR_ARG, "%s: negative refresh", who);
+  if (n_points > 0 && (!cells || !points || !gains)) return set_err(MFGP_ERR_ARG, "%s: null output", who);
+  int rc = MFGP_OK;
+  for (int b = 0; b < count; ++b)
+    if ((rc = check_model(t[b]))) return rc;
+  mfgp_ctx* c = t[0]->ctx;
+  auto too_large = [&](int b) {
+    return ivr_segments(t[b]->M) > 65535 ? set_err(MFGP_ERR_ARG, "%s: grids of at most %lld cells are supported", who,
+                                                   (long long)65535 * IVR_SEG * PBM)
+                                         : MFGP_OK;
+  };
+  // the members' cells and lists: offsets into the grid-sized arrays (moff) and into cand / group (coff)
+  std::vector<int64_t> moff(count), coff(count), ncs(count);
+  int64_t Mtot = 0, maxM = 0, ctot = 0;
+  for (int b = 0; b < count; ++b) {
+    if (t[b]->ctx != c) return set_err(MFGP_ERR_ARG, "%s: batch models must share one context", who);
+    for (int b2 = 0; b2 < b; ++b2)
+      if (t[b2] == t[b]) return set_err(MFGP_ERR_ARG, "%s: model %d appears twice in the batch", who, b);
+    if ((rc = need_f64_grid(t[b], who))) return rc;
+    if (!single && (rc = too_large(b))) return rc;
+    moff[b] = Mtot;
+    Mtot += t[b]->M;
+    maxM = std::max(maxM, t[b]->M);
+  }
+  if (!c->incremental) return set_err(MFGP_ERR_ARG, "%s needs incremental updates enabled", who);
+  if (w && ldw < maxM)
+    return set_err(MFGP_ERR_ARG, "%s: ldw = %lld is less than %s = %lld", who, (long long)ldw,
+                   single ? "M" : "the largest M", (long long)maxM);
+  const bool listed = cand || single;   // the counts are cand_off's (the single call's nc: M with a NULL list)
+  if (single && cand_off[1] < 0) return set_err(MFGP_ERR_ARG, "%s: negative candidate count", who);
+  if (cand && !cand_off) return set_err(MFGP_ERR_ARG, "%s: cand needs cand_off", who);
+  if (cand && cand_off[0] != 0) return set_err(MFGP_ERR_ARG, "%s: cand_off[0] must be 0", who);
+  for (int b = 0; b < count; ++b) {
+    if (listed && cand_off[b + 1] < cand_off[b])
+      return set_err(MFGP_ERR_ARG, "%s: cand_off must not decrease (cand_off[%d] = %lld after %lld)", who, b + 1,
+                     (long long)cand_off[b + 1], (long long)cand_off[b]);
+    coff[b] = listed ? cand_off[b] : ctot;
+    ncs[b] = listed ? cand_off[b + 1] - cand_off[b] : t[b]->M;
+    ctot = coff[b] + ncs[b];
+    if (listed && (rc = check_cells(who, "cand", cand ? cand + coff[b] : nullptr, ncs[b], t[b]->M))) return rc;
+  }
+  if (quota && !group) return set_err(MFGP_ERR_ARG, "%s: quota needs group", who);
+  if (group) {
+    if (ngroups < 1 || ngroups > MFGP_PLAN_MAXGROUPS)
+      return set_err(MFGP_ERR_ARG, "%s: ngroups = %d is outside [1, %d]", who, ngroups, MFGP_PLAN_MAXGROUPS);
+    for (int64_t j = 0; j < ctot; ++j)
+      if (group[j] < 0 || group[j] >= ngroups)
+        return set_err(MFGP_ERR_ARG, "%s: group[%lld] = %d is outside [0, %d)", who, (long long)j, (int)group[j],
+                       ngroups);
+    for (int g = 0; quota && g < ngroups; ++g)
+      if (quota[g] < 0) return set_err(MFGP_ERR_ARG, "%s: quota[%d] is negative", who, g);
+  }
+  const bool w_host = w && !is_device_ptr(w);
+  for (int b = 0; w_host && b < count; ++b)
+    if (finite_rows(w + (int64_t)b * ldw, 1, ldw, t[b]->M) >= 0)
+      return single ? set_err(MFGP_ERR_ARG, "%s: the weights must be finite", who)
+                    : set_err(MFGP_ERR_ARG, "%s: the weights must be finite (member %d)", who, b);
+  if (single && (rc = too_large(0))) return rc;
+  for (int b = 0; b < count; ++b) counts[b] = 0;
+  if (n_points == 0 || (single && ncs[0] == 0)) return MFGP_OK;
+  if ((rc = plan_ready(c, t, count))) return rc;
+  std::vector<int64_t> N0(count);
+  for (int b = 0; b < count; ++b) {
+    if ((rc = ensure_resident_v(t[b], who))) return rc;
+    N0[b] = t[b]->NL + t[b]->NH;
+    if ((rc = ensure_cap(t[b], N0[b] + std::min<int64_t>(n_points, PLAN_CHUNK))) || (rc = ensure_v(t[b]))) return rc;
+  }
+  // device state: mu, var, S, g, x [sum M] | tau's partials | vmax, vargmax [B] | state [B][2] | xn [B][2] |
+  // yn [B] | cells, pos, gains [B][P] | points [B][P][2] | cand | group | quota | the group counters
+  // [B][groups] | host weights [B][max M] | the members' descriptors | k_ivr_partial's partials (the
+  // largest member's: the members' GEMMs follow one another) | each member's covariance-product
+  // scratch | the saved resident posteriors
+  const size_t P = (size_t)n_points, B = (size_t)count, dM = sizeof(double) * (size_t)Mtot;
+  const size_t NG = group ? (size_t)ngroups : 0;
+  std::vector<int64_t> toff(count);
+  std::vector<size_t> o_work(count);
+  int64_t ntau_tot = 0;
+  size_t part_max = 0, nres = 0;
+  for (int b = 0; b < count; ++b) {
+    toff[b] = ntau_tot;
+    ntau_tot += plan_tau_parts(t[b]->M);
+    part_max = std::max(part_max, (size_t)ivr_segments(t[b]->M) * (size_t)ncs[b]);
+    nres += plan_res_doubles(t[b]);
+  }
+  WsLayout lay;
+  const size_t o_mu = lay.take(dM), o_var = lay.take(dM), o_S = lay.take(dM), o_g = lay.take(dM), o_x = lay.take(dM);
+  const size_t o_tau = lay.take(sizeof(double) * ntau_tot);
+  const size_t o_vmax = lay.take(8 * B), o_varg = lay.take(8 * B), o_state = lay.take(16 * B);
+  const size_t o_xn = lay.take(16 * B), o_yn = lay.take(8 * B);
+  const size_t o_cells = lay.take(8 * B * P), o_pos = lay.take(8 * B * P), o_gains = lay.take(8 * B * P);
+  const size_t o_pts = lay.take(16 * B * P);
+  const size_t o_cand = lay.take(cand ? sizeof(int64_t) * ctot : 0);
+  const size_t o_group = lay.take(group ? sizeof(int32_t) * ctot : 0);
+  const size_t o_quota = lay.take(8 * NG), o_gcnt = lay.take(8 * B * NG);
+  const size_t o_w = lay.take(w_host ? sizeof(double) * B * maxM : 0);
+  const size_t o_desc = lay.take(sizeof(PlanMember) * B);
+  const size_t o_part = lay.take(sizeof(double) * part_max);
+  for (int b = 0; b < count; ++b) o_work[b] = lay.take(cov_work_bytes(t[b], N0[b] + n_points));
+  const size_t o_res = lay.take(sizeof(double) * nres);
+  PlanRun run(who, c, t, count);
+  if (!run.own(lay.end)) return set_err(MFGP_ERR_DEVICE, "%s: out of memory (%zu bytes of scratch)", who, lay.end);
+  double *mu = run.at(o_mu), *var = run.at(o_var), *S = run.at(o_S), *g = run.at(o_g), *x = run.at(o_x);
+  double *tau = run.at(o_tau), *vmax = run.at(o_vmax), *xn = run.at(o_xn), *yn = run.at(o_yn);
+  int64_t *vargmax = run.at<int64_t>(o_varg), *state = run.state = run.at<int64_t>(o_state);
+  int64_t *dcells = run.at<int64_t>(o_cells), *dpos = run.at<int64_t>(o_pos);
+  double *dgains = run.at(o_gains), *dpts = run.at(o_pts);
+  const int64_t* dcand = cand ? run.at<int64_t>(o_cand) : nullptr;
+  const int32_t* dgroup = group ? run.at<int32_t>(o_group) : nullptr;
+  const int64_t* dquota = (group && quota) ? run.at<int64_t>(o_quota) : nullptr;
+  int64_t* dgcnt = group ? run.at<int64_t>(o_gcnt) : nullptr;
+  PlanMember* dm = run.at<PlanMember>(o_desc);
+  hipStream_t s = c->stream;
+  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
+  const StagedIn sw(w, count, maxM, ldw, w_host, run.at(o_w));
+  auto weights_of = [&](int b) -> const double* { return sw.dev ? sw.dev + (int64_t)b * sw.ld : nullptr; };
+  if (sw.upload(s) != hipSuccess ||
+      (cand && hipMemcpyAsync(run.at(o_cand), cand, sizeof(int64_t) * ctot, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      (group && hipMemcpyAsync(run.at(o_group), group, sizeof(int32_t) * ctot, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      (dquota && hipMemcpyAsync(run.at(o_quota), quota, 8 * NG, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      (group && hipMemsetAsync(dgcnt, 0, 8 * B * NG, s) != hipSuccess) ||
+      hipMemsetAsync(S, 0, dM, s) != hipSuccess || run.open() != hipSuccess)
+    return run.fail(set_err(MFGP_ERR_DEVICE, "%s: upload failed", who));
+  // the initial posteriors, and every member's S_0
+  if ((rc = batch_run(const_cast<mfgp_model**>(t), count, nullptr, nullptr, nullptr, mu, var, vmax, vargmax, MFGP_ASYNC,
+                      false, true)))
+    return run.fail(rc);
+  auto numerators = [&](int b) -> int {
+    GPDesc d;
+    fill_desc(d, t[b]);
+    const int64_t* cb = dcand ? dcand + coff[b] : nullptr;
+    HIP_TRY(launch_ivr_partial(d, cb, ncs[b], weights_of(b), 1, t[b]->M, run.at(o_part), s));
+    HIP_TRY(launch_plan_scatter(run.at(o_part), (int)ivr_segments(t[b]->M), ncs[b], cb, S + moff[b], s));
+    return MFGP_OK;
+  };
+  std::vector<CovWork> cw(count);
+  bool any_sep = false;
+  for (int b = 0; b < count; ++b) {
+    if ((rc = numerators(b)) || (rc = cov_work_init(t[b], run.ws + o_work[b], N0[b] + n_points, cw[b])))
+      return run.fail(rc);
+    any_sep = any_sep || cw[b].sep;
+    t[b]->gate_dev = reinterpret_cast<int*>(state + 2 * b);
+  }
+  // member b's arguments as of this chunk (V, its leading dimension and the status word may move
+  // when the capacity grows), with its row at place `place` of xn / yn
+  auto describe = [&](int b, int place) {
+    PlanMember m{};
+    m.a = cw[b].a;
+    m.a.V = static_cast<const double*>(t[b]->V.get());
+    m.a.vld = t[b]->vld;
+    m.a.N = N0[b];
+    m.a.x = x + moff[b];
+    m.a.S = S + moff[b];
+    m.a.g = g + moff[b];
+    m.a.tau_part = tau + toff[b];
+    m.a.ntau = (int)plan_tau_parts(t[b]->M);
+    m.a.gate = reinterpret_cast<int*>(state + 2 * b);
+    m.sep = cw[b].sep ? 1 : 0;
+    m.a.kx = m.sep ? cw[b].kx : nullptr;
+    m.k = cw[b].k;
+    m.T = cw[b].T;
+    m.kxo = cw[b].kx;
+    m.nseg = (int)cov_segments(t[b]->M);
+    m.w = weights_of(b);
+    PlanPick& q = m.q;
+    q.S = m.a.S;
+    q.var = var + moff[b];
+    q.mu = mu + moff[b];
+    q.grid = t[b]->grid;
+    q.cand = dcand ? dcand + coff[b] : nullptr;
+    q.nc = ncs[b];
+    q.noise = m.a.h.noiseH;
+    q.jitter = m.a.h.jitter;
+    q.min_gain = min_gain;
+    q.n_points = n_points;
+    q.state = state + 2 * b;
+    q.status = t[b]->status;
+    q.xn = xn + 2 * place;
+    q.yn = yn + place;
+    q.cells = dcells + (size_t)b * P;
+    q.gains = dgains + (size_t)b * P;
+    q.pts = dpts + 2 * (size_t)b * P;
+    q.pos = dpos + (size_t)b * P;
+    q.group = dgroup ? dgroup + coff[b] : nullptr;
+    q.quota = dquota;
+    q.gcount = dgcnt ? dgcnt + (size_t)b * NG : nullptr;
+    return m;
+  };
+  std::vector<int>& live = run.live;
+  int64_t it_done = 0;
+  while (!live.empty() && it_done < n_points) {
+    int64_t C = std::min<int64_t>(PLAN_CHUNK, n_points - it_done);
+    if (refresh > 0) C = std::min<int64_t>(C, refresh - it_done % refresh);
+    std::vector<mfgp_model*> lm;
+    std::vector<int64_t> lk, loff;
+    std::vector<int> lvi;
+    std::vector<PlanMember> hm;
+    int64_t liveM = 0, liveN = 0;
+    for (int b : live) {
+      if ((rc = run.grow(t[b], C))) return run.fail(rc);
+      if (refresh > 0 && it_done > 0 && it_done % refresh == 0 && (rc = numerators(b))) return run.fail(rc);
+      hm.push_back(describe(b, (int)lm.size()));
+      lm.push_back(t[b]);
+      lk.push_back(1);
+      loff.push_back(moff[b]);
+      lvi.push_back(b);
+      liveM = std::max(liveM, t[b]->M);
+      liveN = std::max(liveN, N0[b]);
+    }
+    const int nl = (int)lm.size();
+    if (hipMemcpyAsync(dm, hm.data(), sizeof(PlanMember) * nl, hipMemcpyHostToDevice, s) != hipSuccess)
+      return run.fail(set_err(MFGP_ERR_DEVICE, "%s: upload failed", who));
+    for (int64_t it = 0; it < C; ++it) {
+      if (launch_ivr_pick_batch(dm, nl, s) != hipSuccess)
+        return run.fail(set_err(MFGP_ERR_DEVICE, "%s: launch failed", who));
+      if (nl == count)
+        rc = batch_run(lm.data(), count, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true);
+      else
+        rc = batch_run(lm.data(), nl, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true, loff.data(),
+                       lvi.data());
+      if (rc) return run.fail(rc);
+      if (it_done + it + 1 >= n_points) break;   // the last pick: no score is read after it
+      if (launch_plan_update_batch(dm, nl, it_done + it, liveM, liveN + it_done + it + 1, any_sep, s) != hipSuccess)
+        return run.fail(set_err(MFGP_ERR_DEVICE, "%s: launch failed", who));
+    }
+    it_done += C;
+    if ((rc = run.chunk_end())) return run.fail(rc);
+    std::vector<int> keep;
+    for (int b : live)
+      if ((int)run.st[2 * b] != 0) keep.push_back(b);
+    live.swap(keep);
+  }
+  for (int b = 0; b < count; ++b) {
+    const int64_t n = counts[b] = run.st[2 * b + 1];
+    if (n > 0 && (hipMemcpy(cells + b * P, dcells + b * P, sizeof(int64_t) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(gains + b * P, dgains + b * P, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(points + 2 * b * P, dpts + 2 * b * P, sizeof(double) * 2 * n, hipMemcpyDefault) != hipSuccess ||
+                  (pos && hipMemcpy(pos + b * P, dpos + b * P, sizeof(int64_t) * n, hipMemcpyDeviceToHost) != hipSuccess)))
+      return run.fail(set_err(MFGP_ERR_DEVICE, "%s: copy out failed", who));
+  }
+  // (the posteriors' restore copies read ws)
+  return run.finish(true) == MFGP_OK ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "%s: restore failed", who);
+}
 
 extern "C" {
 
@@ -461,163 +730,21 @@ int mfgp_batch_sample_points(mfgp_model** models, int count, const double* thres
   return left ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "batch_sample_points: restore failed");
 }
 
-// The greedy integrated-variance planner (mfgp_plan_ivr.hip): n_points cells chosen one
-// after another, each the allowed cell whose measurement lowers the weighted posterior
-// variance of the whole grid most, given the picks before it. Each iteration is
-// k_ivr_pick (argmax of S / (var + sigma_H + jitter), the cell and its posterior mean
-// -> the next hifi row, or the gate closed), the general batch step of one model on
-// that row (the lattice step where its gates take it, else the fused V stream), then
-// the rank-one update of the numerators S from one covariance product over the
-// resident V (k_plan_x, k_cov_dot, k_cov_psum, the K** x term, k_cov_apply). S_0 (and
-// every `refresh` picks, S again) is k_ivr_partial's numerators over all cells: the
-// only GEMM. Chunks of iterations are enqueued behind the device gate with one status
-// read per chunk, on the caller's model (plan_enter / plan_leave), as
-// mfgp_sample_points; a chunk ends where a refresh is due.
+// The greedy integrated-variance planner for one model: plan_ivr_run's batch of one, its
+// list the nc cells of cand (NULL: all M), no groups and no recorded positions.
 int mfgp_plan_ivr(mfgp_model* model, const double* w, int64_t ldw, const int64_t* cand, int64_t nc,
                   int64_t n_points, double min_gain, int refresh, int64_t* cells, double* points, double* gains,
                   int64_t* count) {
-  const char* who = "mfgp_plan_ivr";
   const Entry entry(model);
-  int rc = entry.rc;
-  if (rc) return rc;
-  mfgp_model* t = model;
-  mfgp_ctx* c = t->ctx;
-  const int64_t M = t->M;
+  if (entry.rc) return entry.rc;
   if (!count) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: null count");
-  if (n_points < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative n_points");
-  if (refresh < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative refresh");
-  if (n_points > 0 && (!cells || !points || !gains)) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: null output");
-  if ((rc = need_f64_grid(t, who))) return rc;
-  if (!c->incremental) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr needs incremental updates enabled");
-  if (w && ldw < M)
-    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: ldw = %lld is less than M = %lld", (long long)ldw, (long long)M);
-  if (nc < 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: negative candidate count");
-  if ((rc = check_cells(who, "cand", cand, nc, M))) return rc;
-  const bool w_host = w && !is_device_ptr(w);
-  if (w_host && finite_rows(w, 1, ldw, M) >= 0) return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: the weights must be finite");
-  if (ivr_segments(M) > 65535)
-    return set_err(MFGP_ERR_ARG, "mfgp_plan_ivr: grids of at most %lld cells are supported",
-                   (long long)65535 * IVR_SEG * PBM);
-  *count = 0;
-  if (n_points == 0 || nc == 0) return MFGP_OK;
-  if ((rc = plan_ready(c, &t, 1))) return rc;
-  if ((rc = ensure_resident_v(t, who))) return rc;
-  const int64_t N0 = t->NL + t->NH;
-  if ((rc = ensure_cap(t, N0 + std::min<int64_t>(n_points, PLAN_CHUNK))) || (rc = ensure_v(t))) return rc;
-  // device state (the context's workspace serves the lattice step): mu, var, S, g, x [M] | tau's
-  // partials | vmax | vargmax | state {gate, count} | xn [2] | yn | cells, gains [P] | points [P][2] |
-  // cand | host weights | k_ivr_partial's partials | the covariance product's scratch | the
-  // saved resident posterior
-  const int64_t P = n_points, ntau = plan_tau_parts(M), nseg = ivr_segments(M);
-  WsLayout lay;
-  const size_t o_mu = lay.take(sizeof(double) * M), o_var = lay.take(sizeof(double) * M);
-  const size_t o_S = lay.take(sizeof(double) * M), o_g = lay.take(sizeof(double) * M);
-  const size_t o_x = lay.take(sizeof(double) * M), o_tau = lay.take(sizeof(double) * ntau);
-  const size_t o_misc = lay.take(sizeof(double) * 8);
-  const size_t o_cells = lay.take(sizeof(int64_t) * P), o_gains = lay.take(sizeof(double) * P);
-  const size_t o_pts = lay.take(sizeof(double) * 2 * P);
-  const size_t o_cand = lay.take(cand ? sizeof(int64_t) * nc : 0);
-  const size_t o_w = lay.take(w_host ? sizeof(double) * M : 0);
-  const size_t o_part = lay.take(sizeof(double) * (size_t)nseg * M);
-  const size_t o_work = lay.take(cov_work_bytes(t, N0 + P));
-  const size_t o_res = lay.take(sizeof(double) * plan_res_doubles(t));
-  PlanRun run(who, c, &t, 1);
-  if (!run.own(lay.end))
-    return set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: out of memory (%zu bytes of scratch)", lay.end);
-  double *mu_s = run.at(o_mu), *var_s = run.at(o_var), *S = run.at(o_S), *g = run.at(o_g), *x = run.at(o_x);
-  double *tau = run.at(o_tau), *vmax = run.at(o_misc);
-  int64_t* vargmax = reinterpret_cast<int64_t*>(vmax + 1);
-  int64_t* state = run.state = vargmax + 1;
-  double *xn = reinterpret_cast<double*>(state + 2), *yn = xn + 2;
-  int* gate = reinterpret_cast<int*>(state);
-  int64_t* dcand = cand ? run.at<int64_t>(o_cand) : nullptr;
-  hipStream_t s = c->stream;
-  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
-  const StagedIn sw(w, 1, M, ldw, w_host, run.at(o_w));
-  const double* dw = sw.dev;
-  if (sw.upload(s) != hipSuccess ||
-      (cand && hipMemcpyAsync(dcand, cand, sizeof(int64_t) * nc, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      run.open() != hipSuccess)
-    return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: upload failed"));
-  // the initial posterior, and S_0
-  if ((rc = batch_run(&t, 1, nullptr, nullptr, nullptr, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, false, true)))
-    return run.fail(rc);
-  auto numerators = [&]() -> int {
-    GPDesc d;
-    fill_desc(d, t);
-    HIP_TRY(launch_ivr_partial(d, nullptr, M, dw, 1, M, run.at(o_part), s));
-    HIP_TRY(launch_plan_ssum(run.at(o_part), (int)nseg, M, S, s));
-    return MFGP_OK;
-  };
-  if ((rc = numerators())) return run.fail(rc);
-  CovWork cw;
-  if ((rc = cov_work_init(t, run.ws + o_work, N0 + P, cw))) return run.fail(rc);
-  cw.a.x = x;
-  cw.a.S = S;
-  cw.a.g = g;
-  cw.a.tau_part = tau;
-  cw.a.ntau = (int)ntau;
-  cw.a.gate = gate;
-  PlanPick q{};
-  q.S = S;
-  q.var = var_s;
-  q.mu = mu_s;
-  q.grid = t->grid;
-  q.cand = dcand;
-  q.nc = nc;
-  q.noise = cw.a.h.noiseH;
-  q.jitter = cw.a.h.jitter;
-  q.min_gain = min_gain;
-  q.n_points = n_points;
-  q.state = state;
-  q.status = t->status;
-  q.xn = xn;
-  q.yn = yn;
-  q.cells = run.at<int64_t>(o_cells);
-  q.gains = run.at(o_gains);
-  q.pts = run.at(o_pts);
-  t->gate_dev = gate;
-  const int64_t& done = run.done;
-  bool active = true;
-  const int64_t one = 1;
-  while (active && done < n_points) {
-    int64_t C = std::min<int64_t>(PLAN_CHUNK, n_points - done);
-    if (refresh > 0) C = std::min<int64_t>(C, refresh - done % refresh);
-    if ((rc = run.grow(t, C))) return run.fail(rc);
-    q.status = t->status;
-    if (refresh > 0 && done > 0 && done % refresh == 0 && (rc = numerators())) return run.fail(rc);
-    for (int64_t it = 0; it < C; ++it) {
-      if (launch_ivr_pick(q, s) != hipSuccess) return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
-      if ((rc = batch_run(&t, 1, xn, yn, &one, mu_s, var_s, vmax, vargmax, MFGP_ASYNC, true, true))) return run.fail(rc);
-      if (done + it + 1 >= n_points) break;   // the last pick: no score is read after it
-      const int64_t row = t->NL + t->NH - 1;
-      if (launch_plan_x(static_cast<const double*>(t->V.get()), t->vld, row, M, dw, g, x, tau, gate, s) != hipSuccess)
-        return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: launch failed"));
-      if ((rc = cov_work_run(t, cw, row + 1))) return run.fail(rc);
-    }
-    if ((rc = run.chunk_end(C))) return run.fail(rc);
-    active = (int)run.st[0] != 0;
-  }
-  if (done > 0 && (hipMemcpy(cells, q.cells, sizeof(int64_t) * done, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(gains, q.gains, sizeof(double) * done, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(points, q.pts, sizeof(double) * 2 * done, hipMemcpyDefault) != hipSuccess))
-    return run.fail(set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: copy out failed"));
-  *count = done;
-  // (the posterior's restore copy reads ws)
-  return run.finish(true) == MFGP_OK ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "mfgp_plan_ivr: restore failed");
+  const int64_t cand_off[2] = {0, nc};
+  return plan_ivr_run("mfgp_plan_ivr", true, &model, 1, w, ldw, cand, cand_off, nullptr, nullptr, 0, n_points,
+                      min_gain, refresh, cells, nullptr, points, gains, count);
 }
 
-// mfgp_plan_ivr for a batch of models stepped together, with per-group quotas on the
-// picks (mfgp_plan_ivr.hip's batched kernels). Per iteration: ONE k_ivr_pick_batch (every
-// live member's masked argmax, its next hifi row at its place in xn / yn, or its gate
-// closed), ONE batch step of one row each (as mfgp_batch_sample_points calls it) and ONE
-// launch each of k_plan_x, k_cov_dot, k_cov_psum, k_kss_t, k_kss_out and k_cov_apply in
-// their batched forms, which read each member's arguments from a device array uploaded
-// once per chunk (the row count of an iteration is the member's own plus the iteration's
-// index). S_0, and S again every `refresh` picks, is k_ivr_partial per member over its
-// candidate list, scattered into S at the candidates' cells: no other cell of S is read.
-// A member that stopped leaves the batch at the next chunk boundary; its kernels are
-// no-ops behind its gate meanwhile.
+// mfgp_plan_ivr for a batch of models stepped together, with per-group quotas on the picks
+// (plan_ivr_run).
 int mfgp_batch_plan_ivr(mfgp_model** models, int count, const double* w, int64_t ldw, const int64_t* cand,
                         const int64_t* cand_off, const int32_t* group, const int64_t* quota, int ngroups,
                         int64_t n_points, double min_gain, int refresh, int64_t* cells, int64_t* pos, double* points,
@@ -627,243 +754,8 @@ int mfgp_batch_plan_ivr(mfgp_model** models, int count, const double* w, int64_t
   if (const int rc_ = settle((models && count > 0 && models[0]) ? models[0]->ctx : nullptr)) return rc_;
   if (count <= 0 || !models) return set_err(MFGP_ERR_ARG, "%s: count must be positive and models non-null", who);
   if (!counts) return set_err(MFGP_ERR_ARG, "%s: null counts", who);
-  if (n_points < 0) return set_err(MFGP_ERR_ARG, "%s: negative n_points", who);
-  if (refresh < 0) return set_err(MFGP_ERR_ARG, "%s: negative refresh", who);
-  if (n_points > 0 && (!cells || !points || !gains)) return set_err(MFGP_ERR_ARG, "%s: null output", who);
-  int rc = MFGP_OK;
-  for (int b = 0; b < count; ++b)
-    if ((rc = check_model(models[b]))) return rc;
-  mfgp_ctx* c = models[0]->ctx;
-  mfgp_model* const* t = models;
-  // the members' cells and lists: offsets into the grid-sized arrays (moff) and into cand / group (coff)
-  std::vector<int64_t> moff(count), coff(count), ncs(count);
-  int64_t Mtot = 0, maxM = 0, ctot = 0;
-  for (int b = 0; b < count; ++b) {
-    if (t[b]->ctx != c) return set_err(MFGP_ERR_ARG, "%s: batch models must share one context", who);
-    for (int b2 = 0; b2 < b; ++b2)
-      if (t[b2] == t[b]) return set_err(MFGP_ERR_ARG, "%s: model %d appears twice in the batch", who, b);
-    if ((rc = need_f64_grid(t[b], who))) return rc;
-    if (ivr_segments(t[b]->M) > 65535)
-      return set_err(MFGP_ERR_ARG, "%s: grids of at most %lld cells are supported", who,
-                     (long long)65535 * IVR_SEG * PBM);
-    moff[b] = Mtot;
-    Mtot += t[b]->M;
-    maxM = std::max(maxM, t[b]->M);
-  }
-  if (!c->incremental) return set_err(MFGP_ERR_ARG, "%s needs incremental updates enabled", who);
-  if (w && ldw < maxM)
-    return set_err(MFGP_ERR_ARG, "%s: ldw = %lld is less than the largest M = %lld", who, (long long)ldw,
-                   (long long)maxM);
-  if (cand && !cand_off) return set_err(MFGP_ERR_ARG, "%s: cand needs cand_off", who);
-  if (cand && cand_off[0] != 0) return set_err(MFGP_ERR_ARG, "%s: cand_off[0] must be 0", who);
-  for (int b = 0; b < count; ++b) {
-    if (cand && cand_off[b + 1] < cand_off[b])
-      return set_err(MFGP_ERR_ARG, "%s: cand_off must not decrease (cand_off[%d] = %lld after %lld)", who, b + 1,
-                     (long long)cand_off[b + 1], (long long)cand_off[b]);
-    coff[b] = cand ? cand_off[b] : ctot;
-    ncs[b] = cand ? cand_off[b + 1] - cand_off[b] : t[b]->M;
-    ctot = coff[b] + ncs[b];
-    if (cand && (rc = check_cells(who, "cand", cand + coff[b], ncs[b], t[b]->M))) return rc;
-  }
-  if (quota && !group) return set_err(MFGP_ERR_ARG, "%s: quota needs group", who);
-  if (group) {
-    if (ngroups < 1 || ngroups > MFGP_PLAN_MAXGROUPS)
-      return set_err(MFGP_ERR_ARG, "%s: ngroups = %d is outside [1, %d]", who, ngroups, MFGP_PLAN_MAXGROUPS);
-    for (int64_t j = 0; j < ctot; ++j)
-      if (group[j] < 0 || group[j] >= ngroups)
-        return set_err(MFGP_ERR_ARG, "%s: group[%lld] = %d is outside [0, %d)", who, (long long)j, (int)group[j],
-                       ngroups);
-    for (int g = 0; quota && g < ngroups; ++g)
-      if (quota[g] < 0) return set_err(MFGP_ERR_ARG, "%s: quota[%d] is negative", who, g);
-  }
-  const bool w_host = w && !is_device_ptr(w);
-  for (int b = 0; w_host && b < count; ++b)
-    if (finite_rows(w + (int64_t)b * ldw, 1, ldw, t[b]->M) >= 0)
-      return set_err(MFGP_ERR_ARG, "%s: the weights must be finite (member %d)", who, b);
-  for (int b = 0; b < count; ++b) counts[b] = 0;
-  if (n_points == 0) return MFGP_OK;
-  if ((rc = plan_ready(c, t, count))) return rc;
-  std::vector<int64_t> N0(count);
-  for (int b = 0; b < count; ++b) {
-    if ((rc = ensure_resident_v(t[b], who))) return rc;
-    N0[b] = t[b]->NL + t[b]->NH;
-    if ((rc = ensure_cap(t[b], N0[b] + std::min<int64_t>(n_points, PLAN_CHUNK))) || (rc = ensure_v(t[b]))) return rc;
-  }
-  // device state: mu, var, S, g, x [sum M] | tau's partials | vmax, vargmax [B] | state [B][2] | xn [B][2] |
-  // yn [B] | cells, pos, gains [B][P] | points [B][P][2] | cand | group | quota | the group counters
-  // [B][groups] | host weights [B][max M] | the members' descriptors | k_ivr_partial's partials (the
-  // largest member's: the members' GEMMs follow one another) | each member's covariance-product
-  // scratch | the saved resident posteriors
-  const size_t P = (size_t)n_points, B = (size_t)count, dM = sizeof(double) * (size_t)Mtot;
-  const size_t NG = group ? (size_t)ngroups : 0;
-  std::vector<int64_t> toff(count);
-  std::vector<size_t> o_work(count);
-  int64_t ntau_tot = 0;
-  size_t part_max = 0, nres = 0;
-  for (int b = 0; b < count; ++b) {
-    toff[b] = ntau_tot;
-    ntau_tot += plan_tau_parts(t[b]->M);
-    part_max = std::max(part_max, (size_t)ivr_segments(t[b]->M) * (size_t)ncs[b]);
-    nres += plan_res_doubles(t[b]);
-  }
-  WsLayout lay;
-  const size_t o_mu = lay.take(dM), o_var = lay.take(dM), o_S = lay.take(dM), o_g = lay.take(dM), o_x = lay.take(dM);
-  const size_t o_tau = lay.take(sizeof(double) * ntau_tot);
-  const size_t o_vmax = lay.take(8 * B), o_varg = lay.take(8 * B), o_state = lay.take(16 * B);
-  const size_t o_xn = lay.take(16 * B), o_yn = lay.take(8 * B);
-  const size_t o_cells = lay.take(8 * B * P), o_pos = lay.take(8 * B * P), o_gains = lay.take(8 * B * P);
-  const size_t o_pts = lay.take(16 * B * P);
-  const size_t o_cand = lay.take(cand ? sizeof(int64_t) * ctot : 0);
-  const size_t o_group = lay.take(group ? sizeof(int32_t) * ctot : 0);
-  const size_t o_quota = lay.take(8 * NG), o_gcnt = lay.take(8 * B * NG);
-  const size_t o_w = lay.take(w_host ? sizeof(double) * B * maxM : 0);
-  const size_t o_desc = lay.take(sizeof(PlanMember) * B);
-  const size_t o_part = lay.take(sizeof(double) * part_max);
-  for (int b = 0; b < count; ++b) o_work[b] = lay.take(cov_work_bytes(t[b], N0[b] + n_points));
-  const size_t o_res = lay.take(sizeof(double) * nres);
-  PlanRun run(who, c, t, count);
-  if (!run.own(lay.end)) return set_err(MFGP_ERR_DEVICE, "%s: out of memory (%zu bytes of scratch)", who, lay.end);
-  double *mu = run.at(o_mu), *var = run.at(o_var), *S = run.at(o_S), *g = run.at(o_g), *x = run.at(o_x);
-  double *tau = run.at(o_tau), *vmax = run.at(o_vmax), *xn = run.at(o_xn), *yn = run.at(o_yn);
-  int64_t *vargmax = run.at<int64_t>(o_varg), *state = run.state = run.at<int64_t>(o_state);
-  int64_t *dcells = run.at<int64_t>(o_cells), *dpos = run.at<int64_t>(o_pos);
-  double *dgains = run.at(o_gains), *dpts = run.at(o_pts);
-  const int64_t* dcand = cand ? run.at<int64_t>(o_cand) : nullptr;
-  const int32_t* dgroup = group ? run.at<int32_t>(o_group) : nullptr;
-  const int64_t* dquota = (group && quota) ? run.at<int64_t>(o_quota) : nullptr;
-  int64_t* dgcnt = group ? run.at<int64_t>(o_gcnt) : nullptr;
-  PlanMember* dm = run.at<PlanMember>(o_desc);
-  hipStream_t s = c->stream;
-  if ((rc = run.enter(run.at(o_res)))) return run.fail(rc);
-  const StagedIn sw(w, count, maxM, ldw, w_host, run.at(o_w));
-  auto weights_of = [&](int b) -> const double* { return sw.dev ? sw.dev + (int64_t)b * sw.ld : nullptr; };
-  if (sw.upload(s) != hipSuccess ||
-      (cand && hipMemcpyAsync(run.at(o_cand), cand, sizeof(int64_t) * ctot, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      (group && hipMemcpyAsync(run.at(o_group), group, sizeof(int32_t) * ctot, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      (dquota && hipMemcpyAsync(run.at(o_quota), quota, 8 * NG, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      (group && hipMemsetAsync(dgcnt, 0, 8 * B * NG, s) != hipSuccess) ||
-      hipMemsetAsync(S, 0, dM, s) != hipSuccess || run.open() != hipSuccess)
-    return run.fail(set_err(MFGP_ERR_DEVICE, "%s: upload failed", who));
-  // the initial posteriors, and every member's S_0
-  if ((rc = batch_run(const_cast<mfgp_model**>(t), count, nullptr, nullptr, nullptr, mu, var, vmax, vargmax, MFGP_ASYNC,
-                      false, true)))
-    return run.fail(rc);
-  auto numerators = [&](int b) -> int {
-    GPDesc d;
-    fill_desc(d, t[b]);
-    const int64_t* cb = dcand ? dcand + coff[b] : nullptr;
-    HIP_TRY(launch_ivr_partial(d, cb, ncs[b], weights_of(b), 1, t[b]->M, run.at(o_part), s));
-    HIP_TRY(launch_plan_scatter(run.at(o_part), (int)ivr_segments(t[b]->M), ncs[b], cb, S + moff[b], s));
-    return MFGP_OK;
-  };
-  std::vector<CovWork> cw(count);
-  bool any_sep = false;
-  for (int b = 0; b < count; ++b) {
-    if ((rc = numerators(b)) || (rc = cov_work_init(t[b], run.ws + o_work[b], N0[b] + n_points, cw[b])))
-      return run.fail(rc);
-    any_sep = any_sep || cw[b].sep;
-    t[b]->gate_dev = reinterpret_cast<int*>(state + 2 * b);
-  }
-  // member b's arguments as of this chunk (V, its leading dimension and the status word may move
-  // when the capacity grows), with its row at place `place` of xn / yn
-  auto describe = [&](int b, int place) {
-    PlanMember m{};
-    m.a = cw[b].a;
-    m.a.V = static_cast<const double*>(t[b]->V.get());
-    m.a.vld = t[b]->vld;
-    m.a.N = N0[b];
-    m.a.x = x + moff[b];
-    m.a.S = S + moff[b];
-    m.a.g = g + moff[b];
-    m.a.tau_part = tau + toff[b];
-    m.a.ntau = (int)plan_tau_parts(t[b]->M);
-    m.a.gate = reinterpret_cast<int*>(state + 2 * b);
-    m.sep = cw[b].sep ? 1 : 0;
-    m.a.kx = m.sep ? cw[b].kx : nullptr;
-    m.k = cw[b].k;
-    m.T = cw[b].T;
-    m.kxo = cw[b].kx;
-    m.nseg = (int)cov_segments(t[b]->M);
-    m.w = weights_of(b);
-    PlanPick& q = m.q;
-    q.S = m.a.S;
-    q.var = var + moff[b];
-    q.mu = mu + moff[b];
-    q.grid = t[b]->grid;
-    q.cand = dcand ? dcand + coff[b] : nullptr;
-    q.nc = ncs[b];
-    q.noise = m.a.h.noiseH;
-    q.jitter = m.a.h.jitter;
-    q.min_gain = min_gain;
-    q.n_points = n_points;
-    q.state = state + 2 * b;
-    q.status = t[b]->status;
-    q.xn = xn + 2 * place;
-    q.yn = yn + place;
-    q.cells = dcells + (size_t)b * P;
-    q.gains = dgains + (size_t)b * P;
-    q.pts = dpts + 2 * (size_t)b * P;
-    q.pos = dpos + (size_t)b * P;
-    q.group = dgroup ? dgroup + coff[b] : nullptr;
-    q.quota = dquota;
-    q.gcount = dgcnt ? dgcnt + (size_t)b * NG : nullptr;
-    return m;
-  };
-  std::vector<int>& live = run.live;
-  int64_t it_done = 0;
-  while (!live.empty() && it_done < n_points) {
-    int64_t C = std::min<int64_t>(PLAN_CHUNK, n_points - it_done);
-    if (refresh > 0) C = std::min<int64_t>(C, refresh - it_done % refresh);
-    std::vector<mfgp_model*> lm;
-    std::vector<int64_t> lk, loff;
-    std::vector<int> lvi;
-    std::vector<PlanMember> hm;
-    int64_t liveM = 0, liveN = 0;
-    for (int b : live) {
-      if ((rc = run.grow(t[b], C))) return run.fail(rc);
-      if (refresh > 0 && it_done > 0 && it_done % refresh == 0 && (rc = numerators(b))) return run.fail(rc);
-      hm.push_back(describe(b, (int)lm.size()));
-      lm.push_back(t[b]);
-      lk.push_back(1);
-      loff.push_back(moff[b]);
-      lvi.push_back(b);
-      liveM = std::max(liveM, t[b]->M);
-      liveN = std::max(liveN, N0[b]);
-    }
-    const int nl = (int)lm.size();
-    if (hipMemcpyAsync(dm, hm.data(), sizeof(PlanMember) * nl, hipMemcpyHostToDevice, s) != hipSuccess)
-      return run.fail(set_err(MFGP_ERR_DEVICE, "%s: upload failed", who));
-    for (int64_t it = 0; it < C; ++it) {
-      if (launch_ivr_pick_batch(dm, nl, s) != hipSuccess)
-        return run.fail(set_err(MFGP_ERR_DEVICE, "%s: launch failed", who));
-      if (nl == count)
-        rc = batch_run(lm.data(), count, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true);
-      else
-        rc = batch_run(lm.data(), nl, xn, yn, lk.data(), mu, var, vmax, vargmax, MFGP_ASYNC, true, true, loff.data(),
-                       lvi.data());
-      if (rc) return run.fail(rc);
-      if (it_done + it + 1 >= n_points) break;   // the last pick: no score is read after it
-      if (launch_plan_update_batch(dm, nl, it_done + it, liveM, liveN + it_done + it + 1, any_sep, s) != hipSuccess)
-        return run.fail(set_err(MFGP_ERR_DEVICE, "%s: launch failed", who));
-    }
-    it_done += C;
-    if ((rc = run.chunk_end())) return run.fail(rc);
-    std::vector<int> keep;
-    for (int b : live)
-      if ((int)run.st[2 * b] != 0) keep.push_back(b);
-    live.swap(keep);
-  }
-  for (int b = 0; b < count; ++b) {
-    const int64_t n = counts[b] = run.st[2 * b + 1];
-    if (n > 0 && (hipMemcpy(cells + b * P, dcells + b * P, sizeof(int64_t) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-                  hipMemcpy(gains + b * P, dgains + b * P, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-                  hipMemcpy(points + 2 * b * P, dpts + 2 * b * P, sizeof(double) * 2 * n, hipMemcpyDeviceToHost) !=
-                      hipSuccess ||
-                  (pos && hipMemcpy(pos + b * P, dpos + b * P, sizeof(int64_t) * n, hipMemcpyDeviceToHost) != hipSuccess)))
-      return run.fail(set_err(MFGP_ERR_DEVICE, "%s: copy out failed", who));
-  }
-  // (the posteriors' restore copies read ws)
-  return run.finish(true) == MFGP_OK ? MFGP_OK : set_err(MFGP_ERR_DEVICE, "%s: restore failed", who);
+  return plan_ivr_run(who, false, models, count, w, ldw, cand, cand_off, group, quota, ngroups, n_points, min_gain,
+                      refresh, cells, pos, points, gains, counts);
 }
 
 // Voronoi-cell reductions (simulator.py:194-323) on the device. Inputs may be

@@ -39,14 +39,28 @@ import numpy as np
 from .gaussian_process import MFGP, SFGP
 
 
+def _to_device(models, x_star, f64_for=None):
+    """What every planner here does first: the models' types checked (f64_for: the caller's
+    name, where it needs fp64 models), then each model's data, hyperparameters and the grid
+    ``x_star`` brought to the device -> the grid as a contiguous [M, 2] float64 array."""
+    from . import _lib
+    for m in models:
+        if not isinstance(m, (SFGP, MFGP)):
+            raise TypeError("Invalid model type: must be SFGP or MFGP")
+    for m in models:
+        if f64_for and m._dev().dtype != _lib.F64:
+            raise TypeError(f"{f64_for} needs the fp64 resident V: not available on precision='f32' models")
+    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
+    for m in models:
+        m._sync_data()
+        m._push_hyp()
+        m._grid_to_device(xs)
+    return xs
+
+
 def compute_sample_points(model, x_star, threshold, console):
     """simulator.py:326-374 -> [n, 2] ndarray of the cells to sample, in order."""
-    if not isinstance(model, (SFGP, MFGP)):
-        raise TypeError("Invalid model type: must be SFGP or MFGP")
-    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
-    model._sync_data()
-    model._push_hyp()
-    model._grid_to_device(xs)
+    xs = _to_device([model], x_star)
     # the reference loops until the threshold is met; bound the output buffer
     # generously and refuse to return a truncated answer
     cap = 4 * xs.shape[0] + 1
@@ -66,14 +80,7 @@ def compute_sample_points_batch(models, x_star, thresholds, console=False):
     from . import _lib
     if not models:
         return []
-    for m in models:
-        if not isinstance(m, (SFGP, MFGP)):
-            raise TypeError("Invalid model type: must be SFGP or MFGP")
-    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
-    for m in models:
-        m._sync_data()
-        m._push_hyp()
-        m._grid_to_device(xs)
+    xs = _to_device(models, x_star)
     cap = 4 * xs.shape[0] + 1
     thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(models),))
     pts = _lib.batch_sample_points([m._dev() for m in models], thr, cap)
@@ -96,15 +103,7 @@ def compute_sample_points_ivr(model, x_star, n_points, weights=None, candidates=
     numerators from scratch after every R picks. The model is unchanged, as after
     ``compute_sample_points``; data, hyperparameters and grid reach the device the same way.
     Not available on precision="f32" models (TypeError)."""
-    from . import _lib
-    if not isinstance(model, (SFGP, MFGP)):
-        raise TypeError("Invalid model type: must be SFGP or MFGP")
-    if model._dev().dtype != _lib.F64:
-        raise TypeError("compute_sample_points_ivr needs the fp64 resident V: not available on precision='f32' models")
-    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
-    model._sync_data()
-    model._push_hyp()
-    model._grid_to_device(xs)
+    _to_device([model], x_star, f64_for="compute_sample_points_ivr")
     _, pts, gains = model._dev().plan_ivr(n_points, weights, candidates, min_gain, refresh)
     return pts, gains
 
@@ -126,18 +125,7 @@ def compute_sample_points_ivr_batch(models, x_star, n_points, weights=None, cand
     from . import _lib
     if not models:
         return []
-    for m in models:
-        if not isinstance(m, (SFGP, MFGP)):
-            raise TypeError("Invalid model type: must be SFGP or MFGP")
-    for m in models:
-        if m._dev().dtype != _lib.F64:
-            raise TypeError("compute_sample_points_ivr_batch needs the fp64 resident V: not available on "
-                            "precision='f32' models")
-    xs = np.ascontiguousarray(np.asarray(x_star, dtype=np.float64).reshape(-1, 2))
-    for m in models:
-        m._sync_data()
-        m._push_hyp()
-        m._grid_to_device(xs)
+    _to_device(models, x_star, f64_for="compute_sample_points_ivr_batch")
     n = len(models)
     runs = _lib.batch_plan_ivr([m._dev() for m in models], n_points, weights, candidates, groups, quota, min_gain,
                                refresh)

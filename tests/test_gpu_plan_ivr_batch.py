@@ -9,7 +9,7 @@ ref_t the oracle's from-scratch scores given the device's picks before it,
 Picks of two device runs are compared only on the fixtures whose oracle scores have no near
 ties (tests/test_plan_ivr_batch_host.py asserts that); elsewhere up to the first pick the
 oracle shows decided by rounding. A batch of one member is the single planner bit for bit:
-its step is the same batch_run call and its sums have the same order.
+mfgp_plan_ivr is the same loop entered with one member.
 """
 import ctypes
 
@@ -151,7 +151,9 @@ def test_members_equal_the_single_planner(members, wname, lattice):
     """On the fixtures without near ties every member's cells are those of plan_ivr on the
     member alone and its gains agree within PARITY_TOL, with the step form pinned on both
     sides. Where a batched one-row append + predict gives the single step's bits in that
-    form, cells and gains are equal bit for bit."""
+    form, cells and gains are equal bit for bit. Both entries run the same loop: this guards
+    the single entry's argument mapping, and that a member's sums do not depend on the
+    batch around it."""
     from mfgp_coverage_amd import _lib
     ctx = _lib.Context(0)
     ctx.set_lattice(lattice)
@@ -179,8 +181,10 @@ def test_members_equal_the_single_planner(members, wname, lattice):
 
 
 def test_a_batch_of_one_is_the_single_planner_bit_for_bit():
-    """One member: the same batch step call, the same order of sums. Also group=None against
-    the unconstrained run, and a quota that never binds."""
+    """mfgp_plan_ivr is the batch of one of the same loop, so this guards its argument mapping
+    (count = 1, cand_off = {0, nc}, no groups, no positions) against the batched entry's:
+    equal bits with all cells and with a list. Also group=None against the unconstrained run,
+    and a quota that never binds."""
     from mfgp_coverage_amd import _lib
     for member in (Q.MEMBERS8[0], Q.MEMBERS8[6], Q.MEMBERS8[4]):
         m = _model(member)
@@ -195,6 +199,27 @@ def test_a_batch_of_one_is_the_single_planner_bit_for_bit():
             (c2, p2, t2, g2), = _lib.batch_plan_ivr([m], NPICK, weights=w, groups=np.zeros(nc, dtype=np.int64),
                                                     quota=[NPICK], **kw)
             assert np.array_equal(c2, cells) and np.array_equal(p2, pos) and np.array_equal(g2, gains)
+
+
+def test_the_single_entry_with_a_repeated_cell_and_with_one_cell():
+    """Through mfgp_plan_ivr, a list that names a cell twice and a list of one cell: what the
+    batched entry returns for the same list (the numerators are scattered over the list
+    alone, a repeated cell receiving the same bits twice), and the model's predict bits are
+    those from before."""
+    from mfgp_coverage_amd import _lib
+    member = Q.MEMBERS8[0]                                     # 13 x 11, MF, N = 65
+    m = _build(_lib.context(), member)
+    w = P.weights("mask", 143)
+    mu0, var0 = m.predict()
+    for cand, n in (([71, 20, 71, 5], 6), ([71], 3)):
+        cells, pts, gains = m.plan_ivr(n, weights=w, cand=cand)
+        (bc, bp, bt, bg), = _lib.batch_plan_ivr([m], n, weights=w, cand=cand)
+        assert cells.shape == (n,) and set(cells.tolist()) <= set(cand)
+        assert np.array_equal(cells, bc) and np.array_equal(pts, bt) and np.array_equal(gains, bg)
+        assert np.array_equal(cells, np.asarray(cand)[bp])
+        _check_member(member, w, cand, (cells, bp, pts, gains), n, tag=f"single entry, list {cand}")
+    mu1, var1 = m.predict()
+    assert np.array_equal(mu0, mu1) and np.array_equal(var0, var1)
 
 
 # ---- 3. groups ---------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
-"""Time the greedy integrated-variance planner (mfgp_plan_ivr: k_ivr_pick, the one-row
-batch step, k_plan_x, k_cov_dot, k_cov_psum, k_kss_t / k_kss_out, k_cov_apply) on the
-headline case: the 128 x 128 grid (M = 16384), N = 2048 MF, 64 picks, all cells allowed.
+"""Time the greedy integrated-variance planner through its single entry (mfgp_plan_ivr: the
+batch of one of the loop behind mfgp_batch_plan_ivr, so per pick k_ivr_pick_batch, the one-row
+batch step and the _batch forms of k_plan_x, k_cov_dot, k_cov_psum, k_kss_t / k_kss_out and
+k_cov_apply; KERNELS' substrings match either form) on the headline case: the 128 x 128 grid
+(M = 16384), N = 2048 MF, 64 picks, all cells allowed.
 
 --route new (default): Model.plan_ivr(64), host wall time per call (the call synchronises),
 the median of --reps calls after a warm-up; also one cov_apply of a single vector.
