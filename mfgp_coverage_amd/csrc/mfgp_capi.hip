@@ -136,7 +136,7 @@ int ensure_cap(mfgp_model* m, int64_t need) {
     HIP_TRY(hipMemcpyAsync(X, m->X, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(y, m->y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
   }
-  const bool keep = m->A && m->factored && m->ablk > 0;
+  const bool keep = m->A && m->st.factored && m->st.ablk > 0;
   if (keep) {
     HIP_TRY(hipMemcpy2DAsync(A, sizeof(double) * ld, m->A, sizeof(double) * m->ld, sizeof(double) * m->ld, m->ld,
                              hipMemcpyDeviceToDevice, s));
@@ -144,25 +144,26 @@ int ensure_cap(mfgp_model* m, int64_t need) {
     HIP_TRY(hipMemcpyAsync(zv, m->zv, sizeof(double) * m->cap, hipMemcpyDeviceToDevice, s));
   }
   // the lattice step's F and tables move to the new leading dimension too
-  if (keep && m->F && m->F_n > 0) {
+  const int64_t F_n = m->st.F.n, tab_n = m->st.tab.n;   // (whatever their generation: the rows stay what they were)
+  if (keep && m->F && F_n > 0) {
     if ((rc = dev_alloc(F, s, sizeof(double) * fblk_size(ld), A_ZERO | A_NO_DRAIN))) return rc;
-    for (int64_t jb = 0; 64 * jb < m->F_n; ++jb)   // each column block's rows [64 jb, F_n)
+    for (int64_t jb = 0; 64 * jb < F_n; ++jb)   // each column block's rows [64 jb, F_n)
       HIP_TRY(hipMemcpyAsync(F + fblk_off(jb, ld), m->F + fblk_off(jb, m->F_ld),
-                             sizeof(double) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
+                             sizeof(double) * 64 * (F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
     if (m->Ff) {   // (MFGP_F32: the rows past the build live in Ff only)
       if ((rc = dev_alloc(Ff, s, sizeof(float) * fblk_size(ld), A_ZERO | A_NO_DRAIN))) return rc;
-      for (int64_t jb = 0; 64 * jb < m->F_n; ++jb)
+      for (int64_t jb = 0; 64 * jb < F_n; ++jb)
         HIP_TRY(hipMemcpyAsync(Ff + fblk_off(jb, ld), m->Ff + fblk_off(jb, m->F_ld),
-                               sizeof(float) * 64 * (m->F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
+                               sizeof(float) * 64 * (F_n - 64 * jb), hipMemcpyDeviceToDevice, s));
     }
   }
-  if (m->tab && m->tab_n > 0) {
+  if (m->tab && tab_n > 0) {
     if ((rc = dev_alloc(tab, s, sizeof(double) * 4 * ld * m->tabw, A_ZERO | A_NO_DRAIN))) return rc;
     for (int t = 0; t < 4; ++t)
       HIP_TRY(hipMemcpyAsync(tab + (size_t)t * ld * m->tabw, m->tab + (size_t)t * m->tab_ld * m->tabw,
-                             sizeof(double) * m->tab_n * m->tabw, hipMemcpyDeviceToDevice, s));
+                             sizeof(double) * tab_n * m->tabw, hipMemcpyDeviceToDevice, s));
     if ((rc = dev_alloc(lidx, s, sizeof(int) * ld, A_NO_DRAIN))) return rc;
-    HIP_TRY(hipMemcpyAsync(lidx, m->lidx, sizeof(int) * m->tab_n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(lidx, m->lidx, sizeof(int) * tab_n, hipMemcpyDeviceToDevice, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
   // the commit: nothing below fails; the locals leave with the old buffers and free them
@@ -170,23 +171,22 @@ int ensure_cap(mfgp_model* m, int64_t need) {
   m->F.swap(F);
   m->Ff.swap(Ff);
   m->F_ld = m->F ? ld : 0;
-  if (!m->F) m->F_n = 0;
+  if (!m->F) m->st.f_reallocated();
   m->tab.swap(tab);
   m->tab_ld = m->tab ? ld : 0;
-  if (!m->tab) m->tab_n = 0;
+  if (!m->tab) m->st.tab_reallocated();
   m->X.swap(X);
   m->y.swap(y);
   m->A.swap(A);
   m->Linv.swap(Li);
   m->zv.swap(zv);
   m->iscr.swap(isc);
-  m->l21c_N = -1;
+  m->st.compact_rows_reallocated();
   m->cap = cap;
   m->ld = ld;
   if (!keep) {
-    m->factored = false;
-    m->ablk = 0;
-    m->v_n = 0;
+    m->st.factor_lost(FactorLost::Reallocated);
+    m->st.v_dropped();
   }
   return MFGP_OK;
 }
@@ -203,12 +203,12 @@ int ensure_v(mfgp_model* m) {
   int rc;
   Dev<void> V;   // committed once the valid rows are in it: until then the model keeps its own
   if ((rc = dev_alloc(V, s, es * (size_t)tiles * vld * PBM, A_NO_DRAIN))) return rc;
-  const bool moved = m->V && m->v_n > 0 && m->vtiles >= tiles && m->vld >= m->v_n;
+  const bool moved = m->V && m->st.v_n > 0 && m->vtiles >= tiles && m->vld >= m->st.v_n;
   if (moved)   // capacity grew: move the valid rows of every tile to the new row stride
-    HIP_TRY(hipMemcpy2DAsync(V, es * vld * PBM, m->V, es * m->vld * PBM, es * m->v_n * PBM, tiles,
+    HIP_TRY(hipMemcpy2DAsync(V, es * vld * PBM, m->V, es * m->vld * PBM, es * m->st.v_n * PBM, tiles,
                              hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (!moved) m->v_n = 0;
+  if (!moved) m->st.v_dropped();
   m->V.swap(V);
   V.reset();
   m->vld = vld;
@@ -257,7 +257,7 @@ void fill_desc(GPDesc& d, mfgp_model* m) {
   d.NL = m->NL;
   d.M = m->M;
   d.vld = m->vld;
-  d.ablk = m->ablk;
+  d.ablk = m->st.ablk;
   d.ka = 8;
   d.ksplit = 1;
   d.hf = derive_hyp(m->kind, m->hyp, m->jitter);
@@ -268,7 +268,7 @@ void fill_desc(GPDesc& d, mfgp_model* m) {
 static int ensure_res(mfgp_model* m) {
   if (m->res && m->res_M >= m->M) return MFGP_OK;
   m->res_M = 0;
-  m->res_n[0] = m->res_n[1] = -1;
+  m->st.res_reallocated();
   if (const int rc = dev_alloc(m->res, m->ctx->stream, sizeof(double) * 4 * (size_t)m->M)) return rc;
   m->res_M = m->M;
   return MFGP_OK;
@@ -276,27 +276,13 @@ static int ensure_res(mfgp_model* m) {
 double* res_mu(mfgp_model* m, int b) { return m->res + (size_t)b * 2 * m->res_M; }
 double* res_var(mfgp_model* m, int b) { return m->res + (size_t)b * 2 * m->res_M + m->res_M; }
 // the buffer holding the posterior of the n leading rows (-1: none)
-int res_find(const mfgp_model* m, int64_t n) {
-  for (int b = 0; b < 2; ++b)
-    if (m->res && m->res_n[b] == n && m->res_gen[b] == m->gen) return b;
-  return -1;
-}
-// the buffer a predict writes: not `keep`, else the least recently written
-static int res_out(const mfgp_model* m, int keep) {
-  if (keep >= 0) return 1 - keep;
-  return m->res_tick[0] <= m->res_tick[1] ? 0 : 1;
-}
-void res_tag(mfgp_model* m, int b, int64_t n, int depth) {
-  m->res_n[b] = n;
-  m->res_gen[b] = m->gen;
-  m->res_depth[b] = depth;
-  m->res_tick[b] = ++m->tick;
-}
-// Point a predict descriptor's resident outputs at a buffer (incremental mode);
-// returns the buffer (-1: none). Tag it once the launch is enqueued.
+int res_find(const mfgp_model* m, int64_t n) { return m->res ? m->st.res_find(n) : -1; }
+// Point a predict descriptor's resident outputs at a buffer (incremental mode): not
+// `keep`, else the least recently written; returns the buffer (-1: none). Tag it once
+// the launch is enqueued (predict_enqueued).
 int set_res_out(mfgp_model* m, GPDesc& d, int keep) {
   if (!m->ctx->incremental || m->M <= 0 || ensure_res(m) != MFGP_OK) return -1;
-  const int b = res_out(m, keep);
+  const int b = m->st.res_out(keep);
   d.rmu = res_mu(m, b);
   d.rvar = res_var(m, b);
   return b;
@@ -314,14 +300,16 @@ int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu) {
   // refused allocation leaves the group empty behind an extent that makes the next call
   // allocate again.
   if (!m->F || m->F_ld != ld || (ff && !m->Ff)) {
-    m->F_ld = m->F_n = 0;
+    m->F_ld = 0;
+    m->st.f_reallocated();
     if ((rc = dev_alloc(m->F, s, sizeof(double) * fblk_size(ld), A_ZERO))) return rc;   // F's upper triangle stays zero
     m->Ff.reset();
     if (ff && (rc = dev_alloc(m->Ff, s, sizeof(float) * fblk_size(ld), A_ZERO))) return rc;
     m->F_ld = ld;
   }
   if (!m->tab || m->tab_ld != ld || m->tabw != tabw) {
-    m->tab_ld = m->tabw = m->tab_n = 0;
+    m->tab_ld = m->tabw = 0;
+    m->st.tab_reallocated();
     if ((rc = dev_alloc(m->tab, s, sizeof(double) * 4 * ld * tabw, A_ZERO))) return rc;
     if ((rc = dev_alloc(m->lidx, s, sizeof(int) * ld))) return rc;
     m->tab_ld = ld;
@@ -352,7 +340,7 @@ int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu) {
     m->axt_w = 0;
     if ((rc = dev_alloc(m->axt, s, sizeof(double) * 4 * (tabw + 1) * tabw, A_2M))) return rc;
     m->axt_w = tabw;
-    m->axt_gen = UINT64_MAX;   // build before use
+    m->st.axt_reallocated();
   }
   // Z rows: per part the lattice y-rows (padded to ZKS), then one per training row
   // that could lie off the lattice; zeros where never written (padding rows)
@@ -397,12 +385,11 @@ int ensure_vcol(mfgp_model* m) {
   if (!m->Vc && m->vc_deny_ld == ldc && m->vc_deny_M == M && m->vc_deny_budget == budget) return MFGP_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   // rows of the old store that stay valid at the new stride (the same grid and generation)
-  const int64_t keep =
-      (m->Vc && m->vc_gen == m->gen && m->vc_M == M) ? std::min({m->vc_n, m->v_n, ldc, m->vc_ld}) : 0;
+  const int64_t keep = m->st.vcol_keep(m->Vc && m->vc_M == M, ldc, m->vc_ld);
   Dev<void> old;   // the old store until its kept rows are copied (freed on every return)
   old.swap(m->Vc);
   const int64_t old_ld = m->vc_ld;
-  m->vc_n = 0;
+  m->st.vcol_reallocated();
   m->vc_ld = m->vc_M = 0;
   const size_t es = v_elem(m);
   const int64_t bytes = (int64_t)es * M * ldc;
@@ -414,7 +401,7 @@ int ensure_vcol(mfgp_model* m) {
     // (a failed copy: the new store with no valid rows, vc_ld == 0, so the next call starts over)
     HIP_TRY(hipMemcpy2DAsync(m->Vc, es * ldc, old, es * old_ld, es * keep, M, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    m->vc_n = keep;
+    m->st.vcol_rows_kept(keep);
   }
   old.reset();
   if (!ok) {
@@ -429,7 +416,7 @@ int ensure_vcol(mfgp_model* m) {
 }
 // rows of the store that equal V's now
 int64_t vcol_rows(const mfgp_model* m) {
-  return (m->Vc && m->vc_gen == m->gen && m->vc_ld == m->vld && m->vc_M == m->M) ? std::min(m->vc_n, m->v_n) : 0;
+  return (m->Vc && m->vc_ld == m->vld && m->vc_M == m->M) ? m->st.vcol_rows() : 0;
 }
 int status_error(int st) {
   if (st == INT_MIN)   // wait_flag gave up (mfgp_kernels.hip): a hand-off inside k_inc_stream never arrived
@@ -527,26 +514,20 @@ static void model_out_done(mfgp_model* m, double* mu, double* var, bool host) {
   m->spec_valid = true;
 }
 
-static bool hyp_same(const mfgp_model* m) {
-  return m->factor_jitter == m->jitter && std::memcmp(m->factor_hyp, m->hyp, sizeof(m->hyp)) == 0;
-}
+static_assert(sizeof(mfgp_model::hyp) == sizeof(mfgp_state::ModelState::factor_hyp), "the state compares all of hyp");
 
-bool factor_current(const mfgp_model* m) {
-  return m->factored && m->factor_N == m->NL + m->NH && hyp_same(m);
-}
+bool factor_current(const mfgp_model* m) { return m->st.factor_current(m->NL + m->NH, m->hyp, m->jitter); }
 
 // Rows [factor_N, N) can be appended to the current factor (k_inc_factor).
 bool can_inc_factor(const mfgp_model* m) {
-  const int64_t N = m->NL + m->NH;
-  return m->ctx->incremental && m->factored && hyp_same(m) && m->factor_N < N && N - m->factor_N <= KINC;
+  return m->st.can_inc_factor(m->NL + m->NH, m->hyp, m->jitter, m->ctx->incremental, KINC);
 }
 
 // Predict by one pass over the resident V (k_vstream): V valid for rows < v_n,
 // at most KINC factor rows beyond it (the factor must be current).
 bool can_vstream(const mfgp_model* m) {
-  const int64_t N = m->NL + m->NH;
-  return m->ctx->incremental && m->M > 0 && m->V && m->vtiles >= ntiles_grid(m->M) && m->v_n <= N &&
-         N - m->v_n <= KINC;
+  return m->ctx->incremental && m->M > 0 && m->V && m->vtiles >= ntiles_grid(m->M) &&
+         m->st.can_vstream(m->NL + m->NH, KINC);
 }
 
 bool is_device_ptr(const void* p) {
@@ -731,9 +712,8 @@ int mfgp_ctx_synchronize(mfgp_ctx* c) {
     // a failed factor leaves its model without one: the next use refactors (and
     // raises again), instead of serving the failed factor and its V
     mfgp_model* m = c->async_status[i].m;
-    m->factored = false;
-    m->v_n = 0;
-    m->l21c_N = -1;
+    m->st.factor_lost(FactorLost::AsyncFailed);
+    m->st.v_dropped();
     m->spec_valid = false;
     if (rc == MFGP_OK) rc = status_error(st);
   }
@@ -895,16 +875,12 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
     HIP_TRY(hipMemcpyAsync(m->X, src->X, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(m->y, src->y, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (src->factored && src->ld == m->ld) {
+  if (src->st.factored && src->ld == m->ld) {
     HIP_TRY(hipMemcpyAsync(m->A, src->A, sizeof(double) * src->ld * src->ld, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(m->Linv, src->Linv, sizeof(double) * (src->ld / NB) * TILE, hipMemcpyDeviceToDevice,
                            c->stream));
     HIP_TRY(hipMemcpyAsync(m->zv, src->zv, sizeof(double) * src->cap, hipMemcpyDeviceToDevice, c->stream));
-    m->factored = true;
-    m->factor_N = src->factor_N;
-    m->ablk = src->ablk;
-    std::memcpy(m->factor_hyp, src->factor_hyp, sizeof(m->factor_hyp));
-    m->factor_jitter = src->factor_jitter;
+    m->st.adopt_factor(src->st);
   }
   if (src->M > 0) {
     if ((rc = dev_alloc(m->grid, c->stream, sizeof(double) * 2 * src->M, A_NO_DRAIN))) return rc;
@@ -914,11 +890,11 @@ int mfgp_clone(const mfgp_model* src, mfgp_model** out) {
     m->hax = src->hax;
     m->hay = src->hay;
     // resident V (a deepcopy'd model keeps appending to the copy, sim:339)
-    if (m->factored && src->V && src->v_n > 0 && src->vld == round_up(m->cap, PRB)) {
+    if (m->st.factored && src->V && src->st.v_n > 0 && src->vld == round_up(m->cap, PRB)) {
       if ((rc = ensure_v(m))) return rc;
       HIP_TRY(hipMemcpyAsync(m->V, src->V, v_elem(src) * (size_t)src->vtiles * src->vld * PBM,
                              hipMemcpyDeviceToDevice, c->stream));
-      m->v_n = src->v_n;
+      m->st.adopt_v(src->st);
     }
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -934,7 +910,7 @@ int mfgp_model_set_hyp(mfgp_model* m, const double* hyp, int nhyp, double jitter
     return set_err(MFGP_ERR_ARG, "Hyperparameters must be of length 4 (single-fidelity) or 9 (multi-fidelity)");
   if (jitter != m->jitter || std::memcmp(hyp, m->hyp, sizeof(double) * nhyp) != 0) {
     m->spec_valid = false;
-    m->gen += 1;
+    m->st.new_generation();   // (V's rows stay counted: the factor's hyp test refactors before V is read)
     bump_serial(m);
   }
   std::memcpy(m->hyp, hyp, sizeof(double) * nhyp);
@@ -998,9 +974,9 @@ int mfgp_set_grid(mfgp_model* m, const double* xs, int64_t M) {
   if (M > m->Mcap && (rc = dev_alloc(grown, c->stream, sizeof(double) * 2 * M))) return rc;
   auto old_grid_gone = [m] {
     m->M = 0;
-    m->v_n = 0;   // V columns belong to the previous grid
+    m->st.v_dropped();   // V columns belong to the previous grid
     m->spec_valid = false;
-    m->gen += 1;
+    m->st.new_generation();
     bump_serial(m);
     m->lat = GridLattice{};
     m->hax.clear();
@@ -1046,7 +1022,7 @@ int mfgp_set_data(mfgp_model* m, const double* XL, const double* yL, int64_t NL,
   m->NH = NH;
   if ((rc = copy_rows(m, 0, XL, yL, NL))) return rc;
   if ((rc = copy_rows(m, NL, XH, yH, NH))) return rc;
-  m->factored = false;
+  m->st.factor_lost(FactorLost::RowsReplaced);
   return factor_one(m);
 }
 
@@ -1064,10 +1040,10 @@ int mfgp_append(mfgp_model* m, const double* X, const double* y, int64_t k) {
   m->pred_since_append = false;
   if (k > 0 && (!X || !y)) return set_err(MFGP_ERR_ARG, "null data pointer with k=%lld", (long long)k);
   m->NH += k;
-  if (!m->ctx->incremental) m->factored = false;   // reference behaviour: refactor from scratch
+  if (!m->ctx->incremental) m->st.factor_lost(FactorLost::NotIncremental);   // reference behaviour: refactor from scratch
   const bool staged = m->ctx->deferred && can_inc_factor(m);   // the next factor user runs the append
   const bool sp = !staged && spec && m->ctx->fused && k > 0 && m->M > 0 && can_inc_factor(m) && m->V &&
-                  m->v_n == m->factor_N && m->vtiles >= ntiles_grid(m->M);
+                  m->st.v_at_factor() && m->vtiles >= ntiles_grid(m->M);
   m->NH -= k;
   // the speculative step carries the rows in its launch (batch_run appends them)
   if (sp) return spec_append_predict(m, X, y, k);
@@ -1086,15 +1062,7 @@ int mfgp_truncate(mfgp_model* m, int64_t n_keep_hifi) {
   if (n_keep_hifi != m->NH) {
     m->NH = n_keep_hifi;
     bump_serial(m);
-    // the factor, z and V of the leading rows do not depend on later rows
-    const int64_t N = m->NL + m->NH;
-    if (m->factored && m->factor_N > N) m->factor_N = N;
-    m->v_n = std::min(m->v_n, N);
-    m->F_n = std::min(m->F_n, N);
-    m->vc_n = std::min(m->vc_n, N);
-    m->tab_n = std::min(m->tab_n, N);
-    for (int b = 0; b < 2; ++b)
-      if (m->res_n[b] > N) m->res_n[b] = -1;   // the posterior of rows that are gone
+    m->st.rows_cut(m->NL + m->NH);
   }
   return MFGP_OK;
 }
@@ -1196,7 +1164,7 @@ int mfgp_predict(mfgp_model* m, double* mu, double* var) {
     rc = batch_run(&m, 1, nullptr, nullptr, nullptr, kmu, kvar, nullptr, nullptr, MFGP_ASYNC, true, true);
     if (rc == MFGP_OK) rc = mfgp_ctx_synchronize(c);
     if (rc == MFGP_OK) model_out_done(m, mu, var, host);
-    if (rc != MFGP_OK) m->factored = false;   // a failed step leaves no usable factor
+    if (rc != MFGP_OK) m->st.factor_lost(FactorLost::StepFailed);   // a failed step leaves no usable factor
     return rc;
   }
   if ((rc = update_factor(m))) return rc;
@@ -1220,9 +1188,7 @@ int mfgp_predict(mfgp_model* m, double* mu, double* var) {
   if ((rc = upload_slot(c, slot, 1, &dd))) return rc;
   if ((rc = vst ? enqueue_vstream(c, dd, hd, 1) : enqueue_predict(c, dd, hd, 1))) return rc;
   (vst ? m->cnt[N_VSTREAM] : m->cnt[N_FULL_PREDICT]) += 1;
-  if (!vst) m->vc_n = 0;   // (a full predict rewrote V: the column store starts over)
-  m->v_n = m->NL + m->NH;
-  if (rb >= 0) res_tag(m, rb, m->v_n, 0);
+  m->st.predict_enqueued(vst ? Predict::VStream : Predict::Full, m->NL + m->NH, rb);
   if ((rc = release_slot(c, slot))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   model_out_done(m, mu, var, host);
@@ -1251,7 +1217,7 @@ int mfgp_model_stats(const mfgp_model* m, int64_t* out, int n) {
     if (m->kind == MFGP_MF) HIP_TRY(hipMemcpy(&nv[1], m->zvl + m->zb_rows + 1, sizeof(int), hipMemcpyDeviceToHost));
     virt = (int64_t)nv[0] + nv[1];
   }
-  const int64_t v[20] = {m->factored ? m->factor_N : -1, m->v_n, m->cnt[N_FULL_FACTOR], m->cnt[N_INC_FACTOR],
+  const int64_t v[20] = {m->st.factored ? m->st.factor_N : -1, m->st.v_n, m->cnt[N_FULL_FACTOR], m->cnt[N_INC_FACTOR],
                          m->cnt[N_FULL_PREDICT], m->cnt[N_VSTREAM], m->lat.nx, m->lat.ny, m->cnt[N_LATTICE], virt,
                          m->cnt[N_LATTICE_ARG], m->cnt[N_LATTICE_G2], m->cnt[N_POST_COPY], m->cnt[N_EARLY_PD],
                          m->cnt[N_LOOK_BORDER], m->cnt[N_LOOK_QUERY], m->cnt[N_SAMPLE_SOLVE], m->cnt[N_SAMPLE_GEMM],
@@ -1267,7 +1233,7 @@ int mfgp_debug_read_v(mfgp_model* m, double* v_out, double* vc_out, int64_t n_ma
   int rc = entry.rc;
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-  const int64_t n = m->V ? std::min(m->v_n, std::max<int64_t>(n_max, 0)) : 0, M = m->M;
+  const int64_t n = m->V ? std::min(m->st.v_n, std::max<int64_t>(n_max, 0)) : 0, M = m->M;
   const int64_t vcn = vcol_rows(m);
   if (rows) *rows = n;
   if (vc_rows) *vc_rows = vcn;
@@ -1299,7 +1265,7 @@ int mfgp_debug_read_f(mfgp_model* m, double* f_out, int64_t n_max, int64_t* rows
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(m->ctx->stream));
   const bool ff = m->dtype == MFGP_F32 && m->Ff;
-  const int64_t n = (m->F && m->F_gen == m->gen) ? std::min(m->F_n, std::max<int64_t>(n_max, 0)) : 0;
+  const int64_t n = m->F ? std::min(m->st.F.rows(m->st.gen), std::max<int64_t>(n_max, 0)) : 0;
   if (rows) *rows = n;
   if (!f_out || n == 0) return MFGP_OK;
   const int64_t ld = m->F_ld, tot = fblk_size(ld);

@@ -27,6 +27,7 @@
 #include "../../include/mfgp_hip.h"
 #include "mfgp_internal.h"
 #include "mfgp_own.h"
+#include "mfgp_state.h"
 
 namespace mfgp_host __attribute__((visibility("hidden"))) {
 
@@ -168,6 +169,9 @@ enum PathCounter {
   N_SAMPLE_GEMM,
   N_COUNTERS
 };
+
+using mfgp_state::FactorLost;
+using mfgp_state::Predict;
 
 }  // namespace mfgp_host
 
@@ -321,27 +325,25 @@ struct mfgp_model {
   mfgp_host::Pin<int> status_host;       // mapped pinned words the single-GP fused launch publishes into:
                                     // [0] its status (last act), [1] the L22 verdict (pd_host)
   int* status_host_dev = nullptr;   // its device address (an alias of status_host, not owned)
-  bool factored = false;
-  int64_t factor_N = -1;    // rows [0, factor_N) of A / Linv / zv hold the current factor
-  int64_t ablk = 0;         // 64-row blocks of A / Linv initialised (assembled or padded)
-  double factor_hyp[9] = {0};
-  double factor_jitter = 0.0;
+  // which rows of the derived buffers below are current (the factor, V, the compact rows,
+  // F, the tables, the column store, the resident posterior): mfgp_state.h, the one place
+  // that changes it
+  mfgp_state::ModelState st;
   // grid (device)
   int64_t M = 0, Mcap = 0;
   mfgp_host::Dev<double> grid;
   mfgp::GridLattice lat{};        // lattice structure of the grid (nx == 0: none)
   std::vector<double> hax, hay;   // the lattice's axis values (host copy, for rows_on_cells)
   // resident V = L^-1 psi^T [vtiles][vld][PBM] (double, or float for MFGP_F32);
-  // rows [0, v_n) valid for the current factor and grid
+  // rows [0, st.v_n) valid for the current factor and grid
   mfgp_host::Dev<void> V;
-  int64_t vld = 0, vtiles = 0, v_n = 0;
+  int64_t vld = 0, vtiles = 0;
   mfgp_host::Dev<double> tred;     // [vtiles][2] per-tile (max, argmax) of var, then the tiles' arrival counter
   int64_t tred_n = 0;         // doubles of tred
   mfgp_host::Dev<unsigned> sync;   // k_inc_stream hand-off words {arrivals, L21 ready, L22 ready} (zeroed)
   unsigned epoch = 0;         // last k_inc_stream epoch of this model
-  // the compact bordered rows in iscr (inc_l21c_offset) hold rows [l21c_n0, l21c_N)
-  // bordered onto l21c_n0 factor rows (-1: none)
-  int64_t l21c_n0 = -1, l21c_N = -1;
+  // (the compact bordered rows in iscr, inc_l21c_offset: rows [st.l21c_n0, st.l21c_N)
+  // bordered onto st.l21c_n0 factor rows)
   // speculative predict: an (eager) append that follows the pattern append ->
   // predict runs the bordered append and the one-pass predict as one launch and
   // keeps mu | var in `spec_out` (mapped pinned, [2][M]) for the predict that
@@ -360,30 +362,21 @@ struct mfgp_model {
   mfgp_look_rec* look = nullptr;   // look-ahead record (allocated by the first mfgp_query, not cloned)
   mfgp_sample_rec* samp = nullptr;   // sample record (allocated by the first mfgp_sample_*, not cloned)
   mfgp_host::Dev<unsigned> csr;     // the scan units' member lists (csr_bytes; mfgp_internal.h)
-  // state generation: a new factor from scratch, a new grid or new hyperparameters
-  // start a new one (the resident posterior, F and the tables belong to one)
-  uint64_t gen = 1;
   // posterior serial (mfgp_model_serial): a process-wide fresh value at every change
   // of the rows, hyperparameters, jitter or grid -- unlike (gen, N) it never repeats
   // (truncate + append of the same count), so a holder of an earlier predict's
   // result can tell whether the model still holds that posterior
   uint64_t serial = 0;
   // resident posterior: two buffers [mu | var] of M each, written by every predict
-  // (incremental mode); buffer b holds the posterior of the res_n[b] leading rows
+  // (incremental mode); buffer b holds the posterior of the st.res[b].n leading rows
   mfgp_host::Dev<double> res;
   int64_t res_M = 0;
-  int64_t res_n[2] = {-1, -1};
-  uint64_t res_gen[2] = {0, 0};
-  int res_depth[2] = {0, 0};   // lattice steps since var / mu were computed from V
-  uint64_t res_tick[2] = {0, 0}, tick = 0;
   // lattice-separable step state (allocated on first use)
-  mfgp_host::Dev<double> F;        // explicit L^-1 [F_ld][F_ld], rows [0, F_n) current for generation F_gen
+  mfgp_host::Dev<double> F;        // explicit L^-1 [F_ld][F_ld], rows st.F
   mfgp_host::Dev<float> Ff;        // MFGP_F32: F in fp32 (the rows the lattice steps stream and extend)
-  int64_t F_ld = 0, F_n = 0;
-  uint64_t F_gen = 0;
-  mfgp_host::Dev<double> tab;      // separable tables [4][tab_ld][tabw], rows [0, tab_n)
-  int64_t tab_ld = 0, tabw = 0, tab_n = 0;
-  uint64_t tab_gen = 0;
+  int64_t F_ld = 0;
+  mfgp_host::Dev<double> tab;      // separable tables [4][tab_ld][tabw], rows st.tab
+  int64_t tab_ld = 0, tabw = 0;
   mfgp_host::Dev<double> wv;       // w [wv_ld][KINC]
   int64_t wv_ld = 0;
   mfgp_host::Dev<unsigned> wflag;  // [wv_ld / 64 + 2]
@@ -393,10 +386,9 @@ struct mfgp_model {
   size_t gpart_n = 0;
   mfgp_host::Dev<unsigned> gcnt;   // per GEMM tile
   int64_t gcnt_n = 0;
-  mfgp_host::Dev<int> lidx;   // lattice indices per training row [tab_ld], rows [0, tab_n) (with the tables)
-  mfgp_host::Dev<double> axt;      // axis tables [4][tabw + 1][tabw], current for generation axt_gen
+  mfgp_host::Dev<int> lidx;   // lattice indices per training row [tab_ld], rows st.tab (with the tables)
+  mfgp_host::Dev<double> axt;      // axis tables [4][tabw + 1][tabw], current for generation st.axt_gen
   int64_t axt_w = 0;
-  uint64_t axt_gen = 0;
   mfgp_host::Dev<double> zb;       // Z rows [P][zrows][tabw][zb_ka]
   int64_t zb_rows = 0, zb_w = 0;
   int zb_ka = 0;
@@ -404,11 +396,10 @@ struct mfgp_model {
   int64_t zflag_n = 0;
   mfgp_host::Dev<unsigned> ldone;  // [4] lattice phase hand-offs (arrivals | flag, twice)
   mfgp_host::Dev<int> zvl;         // [2][zb_rows + 1]
-  // the column store of V, Vc[cell][vc_ld] in V's element type: rows [0, vc_n) equal V's for
-  // generation vc_gen (allocated with the lattice state where the budget allows: ensure_vcol)
+  // the column store of V, Vc[cell][vc_ld] in V's element type: rows st.vc equal V's
+  // (allocated with the lattice state where the budget allows: ensure_vcol)
   mfgp_host::Dev<void> Vc;
-  int64_t vc_ld = 0, vc_M = 0, vc_n = 0;
-  uint64_t vc_gen = 0;
+  int64_t vc_ld = 0, vc_M = 0;
   int64_t vc_deny_ld = -1, vc_deny_M = -1, vc_deny_budget = -2;   // the shape and budget last refused
 };
 
@@ -505,7 +496,6 @@ void fill_desc(mfgp::GPDesc& d, mfgp_model* m);
 double* res_mu(mfgp_model* m, int b);
 double* res_var(mfgp_model* m, int b);
 int res_find(const mfgp_model* m, int64_t n);
-void res_tag(mfgp_model* m, int b, int64_t n, int depth);
 int set_res_out(mfgp_model* m, mfgp::GPDesc& d, int keep);
 int ensure_lat(mfgp_model* m, int64_t tiles, int ksplit, int ka, int64_t nzu);
 int ensure_vcol(mfgp_model* m);

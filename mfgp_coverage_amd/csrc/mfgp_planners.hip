@@ -27,12 +27,8 @@ using namespace mfgp_host;
 struct PlanSave {
   int64_t NH0 = 0;
   double* res = nullptr;   // device copy of m->res ([2][2][res_M]), or null
-  int64_t res_n[2];
-  uint64_t res_gen[2], res_tick[2], tick;
-  int res_depth[2];
+  mfgp_state::ModelState st;   // what the buffers held (restore_from takes the factor's, V's and the posterior's part)
   bool spec_valid, spec_max, pred_since_append;
-  bool factored;
-  int64_t factor_N, v_n;
   int64_t cnt[N_COUNTERS];   // the path counters
 };
 // doubles of device room plan_enter needs for m's resident posterior
@@ -43,19 +39,10 @@ static int plan_enter(mfgp_model* m, PlanSave& s, double* room) {
   bump_serial(m);   // the loop appends in place: no earlier result's holder may read V meanwhile
   s.res = (m->res && room) ? room : nullptr;
   if (s.res) HIP_TRY(hipMemcpyAsync(s.res, m->res, sizeof(double) * 4 * m->res_M, hipMemcpyDeviceToDevice, m->ctx->stream));
-  for (int b = 0; b < 2; ++b) {
-    s.res_n[b] = m->res_n[b];
-    s.res_gen[b] = m->res_gen[b];
-    s.res_tick[b] = m->res_tick[b];
-    s.res_depth[b] = m->res_depth[b];
-  }
-  s.tick = m->tick;
+  s.st = m->st;
   s.spec_valid = m->spec_valid;
   s.spec_max = m->spec_max;
   s.pred_since_append = m->pred_since_append;
-  s.factored = m->factored;
-  s.factor_N = m->factor_N;
-  s.v_n = m->v_n;
   std::memcpy(s.cnt, m->cnt, sizeof(s.cnt));
   return MFGP_OK;
 }
@@ -85,46 +72,27 @@ static int plan_leave(mfgp_model* m, const PlanSave& s, bool failed = false) {
   std::memcpy(m->cnt, s.cnt, sizeof(s.cnt));
   m->NH = s.NH0;
   bump_serial(m);
-  const int64_t N = m->NL + m->NH;
-  // the factor of the model's own rows is the one it entered with (the loop wrote
-  // rows past them only, also in a step that failed); V likewise, and what the loop's
-  // first predict built of it stays. INVARIANT this relies on: between plan_enter and
-  // here nothing drops the factor or V's leading rows for real -- ensure_cap keeps a
-  // factored model's factor (its !keep branch needs !factored, and plan_enter runs
-  // after update_factor), ensure_v copies the valid rows when only the capacity grew
-  // (its drop branch needs another grid or no V, and then s.v_n is 0 already), and the
-  // loops fail on "factor lost on growth". A path that could drop either inside the
-  // loop must clear s.factored / s.v_n too, or this restore would resurrect them.
-  m->factored = s.factored;
-  m->factor_N = std::min(s.factor_N, N);
-  m->v_n = std::max(std::min(m->v_n, N), std::min(s.v_n, N));
-  m->F_n = std::min(m->F_n, N);
-  m->vc_n = std::min(m->vc_n, N);
-  m->tab_n = std::min(m->tab_n, N);
-  m->l21c_N = -1;   // (the compact rows in iscr are the loop's now)
+  // the factor and V of the model's own rows are the ones it entered with, the posterior
+  // buffers too where they were saved (ModelState::restore_from, with its invariant: kept
+  // today because ensure_cap keeps a factored model's factor, ensure_v moves V's valid rows
+  // when only the capacity grew, and the loops fail on "factor lost on growth")
+  const bool posterior = s.res && m->res;
+  const bool kept = m->st.restore_from(s.st, m->NL + m->NH, posterior);
   if (failed) {
     // a failed step left its verdict in the status word: the kept factor is a valid
     // one, and the next loop's first decision reads the word before any append resets it
     static const int ok = INT_MAX;
     HIP_TRY(hipMemcpyAsync(m->status, &ok, sizeof(int), hipMemcpyHostToDevice, m->ctx->stream));
   }
-  if (s.res && m->res) {
+  if (posterior && kept)
     HIP_TRY(hipMemcpyAsync(m->res, s.res, sizeof(double) * 4 * m->res_M, hipMemcpyDeviceToDevice, m->ctx->stream));
-    for (int b = 0; b < 2; ++b) {
-      m->res_n[b] = s.res_n[b];
-      m->res_gen[b] = s.res_gen[b];
-      m->res_tick[b] = s.res_tick[b];
-      m->res_depth[b] = s.res_depth[b];
-    }
-    m->tick = std::max(m->tick, s.tick);
-  } else {
-    for (int b = 0; b < 2; ++b)
-      if (m->res_n[b] > N) m->res_n[b] = -1;
-  }
   // the kept result of the model's last predict: spec_out is not written by the loop
   m->spec_valid = s.spec_valid && factor_current(m);
   m->spec_max = s.spec_max && m->spec_valid;
   m->pred_since_append = s.pred_since_append;
+  if (!kept)
+    return set_err(MFGP_ERR_DEVICE, "planner restore: the factor or V's leading rows were dropped inside the loop "
+                                    "(the invariant of ModelState::restore_from); the model is cut to its rows");
   return MFGP_OK;
 }
 
@@ -567,7 +535,7 @@ int mfgp_sample_points(mfgp_model* model, double threshold, int64_t max_points, 
       pd.vmax = vmax;
       pd.vargmax = vargmax;
       pd.gate = gate;
-      t->v_n = t->NL + t->NH;
+      t->st.predict_enqueued(Predict::VStream, t->NL + t->NH);
     }
     set_rsplit(c, hd + 1, 1);
     for (int64_t i = 0; i < 2 * C; ++i) hd[i].rsplit = hd[1].rsplit;

@@ -17,7 +17,7 @@ namespace mfgp_host __attribute__((visibility("hidden"))) {   // (as in mfgp_hos
 // V holds all N rows of the current factor, hyperparameters and grid: the state
 // every predict path leaves (mfgp_cov_block reads rows [0, N) of it).
 static bool v_covers(const mfgp_model* m) {
-  return factor_current(m) && m->V && m->v_n == m->NL + m->NH && m->vtiles >= ntiles_grid(m->M);
+  return m->st.v_covers(m->NL + m->NH, m->hyp, m->jitter) && m->V && m->vtiles >= ntiles_grid(m->M);
 }
 
 // Bring V over all N rows, as mfgp_predict would (a pending or deferred append, new
@@ -31,7 +31,7 @@ int ensure_resident_v(mfgp_model* m, const char* who) {
   if ((rc = mfgp_predict(m, m->spec_out, m->spec_out + m->spec_cap))) return rc;
   if (!v_covers(m))
     return set_err(MFGP_ERR_NO_V, "%s: the resident V holds %lld of the model's %lld rows after a predict", who,
-                   (long long)m->v_n, (long long)(m->NL + m->NH));
+                   (long long)m->st.v_n, (long long)(m->NL + m->NH));
   return MFGP_OK;
 }
 

@@ -109,8 +109,7 @@ static bool lat_eligible(const mfgp_model* m, int64_t n0) {
   if (lat_tabw(m) > NT) return false;   // a Z unit's thread per lattice column
   if ((n0 + 63) / 64 > LAT_NWB_MAX) return false;   // a w unit's blocks
   if (!lat_cond_ok(m)) return false;
-  const int b = res_find(m, n0);
-  return b >= 0 && m->res_depth[b] < LAT_MAXD;
+  return m->res && m->st.lat_depth_ok(n0, LAT_MAXD);
 }
 // The kernels' uniform test (inc_gather_fast, lat_wblock) on the host, for the path counter:
 // is every new row the lattice cell its rounded axis estimate names? Rows the host does not
@@ -380,20 +379,14 @@ void set_rsplit(const mfgp_ctx* c, GPDesc* hd, int count) {
 
 static void mark_full_factor(mfgp_model* m) {
   m->cnt[N_FULL_FACTOR] += 1;
-  m->gen += 1;   // a factor from scratch: new rounding of everything derived from it
-  m->factored = true;
-  m->factor_N = m->NL + m->NH;
-  std::memcpy(m->factor_hyp, m->hyp, sizeof(m->hyp));
-  m->factor_jitter = m->jitter;
-  m->ablk = std::max(m->ablk, nblocks_factor(m->factor_N));
-  m->v_n = 0;   // V belonged to the previous factor
-  m->l21c_N = -1;
+  const int64_t N = m->NL + m->NH;
+  m->st.full_factor_enqueued(N, nblocks_factor(N), m->hyp, m->jitter);
 }
 
 void mark_inc_factor(mfgp_model* m) {
   m->cnt[N_INC_FACTOR] += 1;
-  m->factor_N = m->NL + m->NH;
-  m->ablk = std::max(m->ablk, nblocks_factor(m->factor_N));
+  const int64_t N = m->NL + m->NH;
+  m->st.inc_factor_enqueued(N, nblocks_factor(N));
 }
 
 // Descriptor of a bordered append of rows [factor_N, N) (k_inc_stream; the
@@ -402,23 +395,22 @@ int fill_inc_desc(GPDesc& d, mfgp_model* m) {
   int rc = ensure_sync(m);
   if (rc) return rc;
   fill_desc(d, m);
-  d.n0 = m->factor_N;
-  d.vres = m->V ? m->v_n : 0;
+  d.n0 = m->st.factor_N;
+  d.vres = m->V ? m->st.v_n : 0;
   d.sync = m->sync;
   if (++m->epoch == 0) m->epoch = 1;
   d.epoch = m->epoch;
   d.nprod = (int)fused_producers(d.n0);
   d.l21c_ok = 1;   // the producers write the compact rows for (n0, N)
-  m->l21c_n0 = d.n0;
-  m->l21c_N = d.N;
+  m->st.compact_rows_written(d.n0, d.N);
   return MFGP_OK;
 }
 
 // One-pass predict over the V rows [0, v_n): the compact rows serve it when the
 // last bordered append wrote them for exactly these rows.
 void set_vstream_rows(GPDesc& d, const mfgp_model* m) {
-  d.n0 = m->v_n;
-  d.l21c_ok = (m->l21c_n0 == m->v_n && m->l21c_N == m->NL + m->NH) ? 1 : 0;
+  d.n0 = m->st.v_n;
+  d.l21c_ok = m->st.l21c_ok(m->NL + m->NH) ? 1 : 0;
 }
 
 // Factor one model now (synchronous, status checked).
@@ -437,7 +429,7 @@ int factor_one(mfgp_model* m) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   mark_full_factor(m);
   rc = read_status(m);
-  m->factored = (rc == MFGP_OK);
+  m->st.factor_checked(rc == MFGP_OK);
   return rc;
 }
 
@@ -458,7 +450,7 @@ int update_factor(mfgp_model* m) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   mark_inc_factor(m);
   rc = read_status(m);
-  m->factored = (rc == MFGP_OK);
+  m->st.factor_checked(rc == MFGP_OK);
   return rc;
 }
 
@@ -539,7 +531,7 @@ static int fill_lat_desc(GPDesc& fd, mfgp_model* m, const LatPlan& p, int nwu, i
   fd.nwu = nwu;
   fd.wpart = m->wpart;
   fd.wcnt = m->wcnt;
-  fd.lat_fbuild = (m->F_gen == m->gen && m->F_n >= fd.n0) ? 0 : 1;
+  fd.lat_fbuild = m->st.lat_fbuild(fd.n0) ? 1 : 0;
   fd.lidx = m->lidx;
   fd.axt = m->axt;
   fd.zb = m->zb;
@@ -549,7 +541,7 @@ static int fill_lat_desc(GPDesc& fd, mfgp_model* m, const LatPlan& p, int nwu, i
   fd.zvl = m->zvl;
   fd.nzu = (int)nzu;
   fd.zq = lat_zq(m);
-  fd.lat_axbuild = m->axt_gen == m->gen ? 0 : 1;
+  fd.lat_axbuild = m->st.lat_axbuild() ? 1 : 0;
   fd.lat_selfg = p.selfg;
   if (c->lat_vcol != 0 && m->Vc && m->vc_ld == m->vld && m->vc_M == m->M) {
     fd.vcol = m->Vc;
@@ -566,7 +558,7 @@ static int fill_lat_desc(GPDesc& fd, mfgp_model* m, const LatPlan& p, int nwu, i
   const bool zc = c->lat_zcsr != 0;
   fd.lat_zcsr = (zc && ka == 8 && m->lat.ny <= 256 && m->ld <= 65535) ? 1 : 0;
   fd.csr = m->csr;
-  fd.tab_lo = (m->tab_gen == m->gen) ? std::min(m->tab_n, fd.n0) : 0;
+  fd.tab_lo = m->st.tab_lo(fd.n0);
   return bin;
 }
 
@@ -595,7 +587,7 @@ static int serve_unchanged(mfgp_model** models, int count, const double* X, cons
     mfgp_model* m = models[i];
     const int64_t ki = rows_given ? k[i] : 0;
     const int64_t n = m->NL + m->NH;
-    const int b = (ki == 0 && m->M > 0 && factor_current(m) && m->v_n == n) ? res_find(m, n) : -1;
+    const int b = (ki == 0 && m->M > 0 && factor_current(m) && m->st.v_n == n) ? res_find(m, n) : -1;
     if (b >= 0) {
       pc.push_back({res_mu(m, b), res_var(m, b), mu + oo, var + oo, vmax ? vmax + i : nullptr,
                     vargmax ? vargmax + i : nullptr, m->M});
@@ -714,25 +706,17 @@ static int publish_mapped_status(mfgp_ctx* c, mfgp_model* m, GPDesc& d) {
 void BatchCall::note_predicts(int np, int nv, int nlat, const GPDesc* hd, bool lat_arg, bool g2) {
   for (int i = 0; i < np; ++i) {
     mfgp_model* m = porder[i];
-    m->v_n = m->NL + m->NH;
+    const Predict kind = i < nlat ? Predict::Lattice : (i < nv ? Predict::VStream : Predict::Full);
+    m->st.predict_enqueued(kind, m->NL + m->NH, res_b[i], i < nlat ? res_depth[i] : 0, i < nlat && hd[i].vcol);
     (i < nv ? m->cnt[N_VSTREAM] : m->cnt[N_FULL_PREDICT]) += 1;
-    if (i >= nv) m->vc_n = 0;   // (a full predict rewrote V: the column store starts over)
-    if (res_b[i] >= 0) res_tag(m, res_b[i], m->v_n, i < nlat ? res_depth[i] : 0);
     if (i < nlat) {
       m->cnt[N_LATTICE] += 1;
       if (lat_arg) m->cnt[N_LATTICE_ARG] += 1;
       if (g2) m->cnt[N_LATTICE_G2] += 1;
-      m->F_n = m->v_n;   // F's new rows and the new rows' tables came with the step
-      m->F_gen = m->gen;
       if (hd[i].vcol) {   // caught up to n0 ahead of the step, the new rows written through
         m->cnt[N_VCOL_ROWS] += hd[i].n0 - hd[i].vcol_lo;
         m->cnt[N_LATTICE_VCOL] += (hd[i].lat_vcol && rows_on_cells(m, hd[i])) ? 1 : 0;
-        m->vc_n = m->v_n;
-        m->vc_gen = m->gen;
       }
-      m->tab_n = m->v_n;
-      m->tab_gen = m->gen;
-      m->axt_gen = m->gen;
     }
   }
 }
@@ -783,7 +767,7 @@ int BatchCall::sub_batch(int b0, int nb) {
   // resident up to the old factor) run as one k_inc_stream launch: their
   // factor descriptors take the predict outputs and the hand-off state
   bool fuse = c->fused && ninc > 0 && ninc == nv;
-  for (int i = 0; fuse && i < ninc; ++i) fuse = order[i] == porder[i] && hd[i].n0 == porder[i]->v_n;
+  for (int i = 0; fuse && i < ninc; ++i) fuse = order[i] == porder[i] && hd[i].n0 == porder[i]->st.v_n;
   if (fuse) {
     for (int i = 0; i < ninc; ++i) {
       GPDesc& fd = hd[i];
@@ -808,7 +792,7 @@ int BatchCall::sub_batch(int b0, int nb) {
     if ((rc = ensure_lat(m, tiles, lp.ksplit, lp.ka, nzu))) return rc;
     const int bin = fill_lat_desc(hd[i], m, lp, lp.nwu[i], tiles, nzu);
     res_b[i] = 1 - bin;
-    res_depth[i] = m->res_depth[bin] + 1;
+    res_depth[i] = m->st.res[bin].depth + 1;
   }
   if (nv > 0) {
     set_rsplit(c, hd + nb, nv);
@@ -828,9 +812,8 @@ int BatchCall::sub_batch(int b0, int nb) {
                                c->stream));
     if ((rc = ev_end(c, ev))) return rc;
     release_slot_unread(c, slot);
-    m->v_n = m->NL + m->NH;
+    m->st.predict_enqueued(Predict::VStream, m->NL + m->NH, res_b[0]);
     m->cnt[N_VSTREAM] += 1;
-    if (res_b[0] >= 0) res_tag(m, res_b[0], m->v_n, 0);
     return MFGP_OK;
   }
   bool lat_arg = false, by_value = false;
@@ -919,7 +902,7 @@ int batch_run(mfgp_model** models, int count, const double* X, const double* y, 
       bump_serial(m);
     }
     off += ki;
-    if (!c->incremental) m->factored = false;   // reference behaviour: refactor every update
+    if (!c->incremental) m->st.factor_lost(FactorLost::NotIncremental);   // reference behaviour: refactor every update
   }
   constexpr int CB = MAXB / 2;   // one descriptor slot per sub-batch: [factor order | predict order]
   for (int b0 = 0; b0 < count; b0 += CB)
@@ -979,7 +962,7 @@ int spec_append_predict(mfgp_model* m, const double* X, const double* y, int64_t
   }
   if (rc == MFGP_OK) rc = mfgp_ctx_synchronize(c);
   if (rc != MFGP_OK) {
-    m->factored = false;   // a failed step leaves no usable factor
+    m->st.factor_lost(FactorLost::StepFailed);   // a failed step leaves no usable factor
     return rc;
   }
   m->spec_valid = true;
